@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- poses/sec of the MI355X-native 6DGS pose path on BASELINE.json's workloads.
 
-  python bench.py --gpus N --steps K --warmup W [--config headline|cfg1|cfg2|cfg3|cfg4]
+  python bench.py --gpus N --steps K --warmup W [--config headline|cfg1|cfg2|cfg3|cfg4] [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank
 per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or started plainly -- then bench.py
@@ -28,9 +28,18 @@ value = (N * batch * K) / time.  Every step ends with the poses on the host.  By
 evaluation is a stream of batches, test.py:46-302): batch N + 1 is submitted -- its image side on a second stream -- before
 batch N's poses are collected (6dgs_amd.test.PoseStream; same poses bit for bit; `--no-pipeline` = one batch at a time with a
 device sync per step, rounds 1-4); `median_step` is then the median interval between the completions of consecutive batches
-(SURVEY §8(d)), `config.pipeline` says which form ran.  Images and scene arrays are resident in HBM when the clock starts.  Rank 0 prints ONE JSON line with `roofline` (the logits kernel: algorithmic FLOP /
-HIP-event time), `fp32_logits_mode` (the same workload with the logits kept in fp32 between the passes instead of
-24-bit fixed point: the cost of not narrowing) and, at N = 1, `cpu_baseline` (the CPU oracle on a bounded ray sample).
+(SURVEY §8(d)), `config.pipeline` says which form ran.  Images and scene arrays are resident in HBM when the clock starts.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the line.
+--full adds the secondary measurements and checks, each after the timed steps: `roofline` (the logits kernel: algorithmic FLOP /
+HIP-event time, from events recorded in the timed steps), `fp32_logits_mode` / `two_pass_mode` (the same workload through the two-pass
+scorer, logits in fp32 / 24-bit fixed point between the passes), `headline_b4` (the other images-per-step setting), `reference_mode`
+(the reference's 1000-ellipsoid emission) and, at N = 1, `cpu_baseline` + `parity_vs_oracle` + `metric_errors` (the CPU oracle on a
+bounded ray sample).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy (float32 / float64):
+c2w (the poses of all ranks), and this rank's topk_indices, topk_weights, up, pose_errors, solve_status.  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -120,6 +129,11 @@ def parse():
                     help="cfg5-standin: score scenes with more rays than this streamed even when their key planes would fit (0 = by HBM size only); lets a "
                          "reduced-scale run exercise the streamed class")
     ap.add_argument("--oracle-rays", type=int, default=1 << 20, help="cfg5-standin: rays of the per-scene oracle check (a prefix of the scene)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (poses, top-k, up vectors, solve status) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary figures and checks (roofline, two-pass / fp32-logits modes, headline_b4, reference mode, CPU baseline "
+                         "and parity against the oracle); a plain run does only the timed steps")
     args = ap.parse_args()
     for k, v in PRESETS[args.config].items():
         if getattr(args, k) is None:
@@ -402,9 +416,11 @@ def main():
         step(None)
         if ps_main is not None and (args.mode == "reference" or (use_select and ops.select_enabled())):      # ... and through the pipelined path itself (its stream, its first graph replay there, its pinned buffers)
             ps_main.collect(ps_main.submit(images, gts))
-    elapsed, per_step, sol = timed(args.steps, None if args.graph else prof)
+    elapsed, per_step, sol = timed(args.steps, prof if (args.full and not args.graph) else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_host[0], sol)
     per_rank_s = dd.all_floats(rank_s[0], dev)          # every rank's own time for the K steps: the line names the slowest rank
-    if args.graph:        # HIP events cannot be read out of a captured graph: the kernel's duration comes from a few EAGER steps of the same batch
+    if args.graph and args.full:        # HIP events cannot be read out of a captured graph: the kernel's duration comes from a few EAGER steps of the same batch
         g_keep, graph = graph, None
         for _ in range(min(args.steps, 5)):
             step(prof)
@@ -418,7 +434,7 @@ def main():
     # ---- the same workload through the two-pass scorer: 24-bit fixed-point logits between the passes, and fp32 logits (VERDICT r1:
     # keep the cost of not narrowing visible).  The select path above stores no logits at all and re-scores its candidates in fp32.
     l32, l24 = None, None
-    n32 = (min(args.steps, 3) if args.l32_steps < 0 else args.l32_steps) if (mode == ops.MMA_F16X3 and not args.graph and not streamed and not ray_sharded) else 0
+    n32 = (min(args.steps, 3) if args.l32_steps < 0 else args.l32_steps) if (args.full and mode == ops.MMA_F16X3 and not args.graph and not streamed and not ray_sharded) else 0
     if n32 > 0:
         two_pass_ws()
         ops.set_select_enabled(False)
@@ -502,7 +518,7 @@ def main():
     # tail is paid once per 8 poses; 16 = two such launches, measured equal: profiles/r06_images_per_step.md) and `headline_b4` is the 4-image figure
     # of rounds 1-5 for continuity (with --batch 4 the roles swap: `headline_b8`).  Same path, same pipeline.
     alt = 4 if args.batch == 8 else 8
-    if args.config == "headline" and pipelined and args.b8_steps != 0 and args.mode == "full":
+    if args.full and args.config == "headline" and pipelined and args.b8_steps != 0 and args.mode == "full":
         camsa = syn.make_cameras(alt, 500 + rank, width=args.image_size, height=args.image_size)
         imagesa = [torch.from_numpy(c["image"]).to(dev) for c in camsa]
         gtsa = torch.stack([tp.gt_pose_and_intrinsics(pkg.CameraInfo(**c), dev)[0] for c in camsa]).to(dev)
@@ -525,7 +541,7 @@ def main():
         out["two_pass_mode"] = l24
     if l32 is not None:
         out["fp32_logits_mode"] = l32
-    if rank == 0:
+    if rank == 0 and args.full:
         traffic, traffic_source = None, None
         if os.path.exists(args.traffic_json):
             try:
@@ -568,10 +584,10 @@ def main():
                                               "the same batch right after them" % min(args.steps, 5))
     # ---- secondary figure: the reference's own emission (1000 sampled ellipsoids, quadricell: R ~ 28.7 k), where the per-pose cost is
     # the image side (ViT + CNN) and launch overhead, not the scorer.  Every rank runs it (image-sharded like the headline).
-    if args.mode == "full" and not args.skip_reference_mode and not streamed and not args.graph and not ray_sharded:
+    if args.full and args.mode == "full" and not args.skip_reference_mode and not streamed and not args.graph and not ray_sharded:
         out["reference_mode"] = reference_mode_figure(args, pkg, syn, tp, dd, idm, scene, dev, rank, world)
     if rank == 0:
-        if world == 1 and not args.skip_cpu_baseline and not ray_sharded:
+        if args.full and world == 1 and not args.skip_cpu_baseline and not ray_sharded:
             out["cpu_baseline"], out["parity_vs_oracle"] = cpu_baseline(args, idm, ori, dr, rgb, R, sol, gts)
             # BASELINE.json's metric is "poses/sec ...; mean rot/trans err": the second half, answered from this line alone
             pv = out["parity_vs_oracle"]
@@ -583,6 +599,20 @@ def main():
                                             "truth says nothing about accuracy -- it is the same number on both paths, which is the point"}
         print(json.dumps(out), flush=True)
     dd.barrier()
+
+
+def dump_outputs(out_dir, c2w_host, sol) -> None:
+    """What the last timed step returned, as float32 / float64 .npy files (indices and status codes as float64: exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"c2w": c2w_host}
+    for name, key in (("topk_indices", "idx"), ("topk_weights", "weights"), ("up", "up"), ("pose_errors", "errors"), ("solve_status", "status")):
+        if isinstance(sol, dict) and sol.get(key) is not None:
+            arrays[name] = sol[key]
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype.kind in "iub" or a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def reference_mode_figure(args, pkg, syn, tp, dd, idm, scene, dev, rank, world, batch: int = 16, steps: int = 10):

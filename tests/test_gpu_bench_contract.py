@@ -39,7 +39,7 @@ def _run(cmd, env=None, timeout=400):
 def test_bench_single_gpu_json_contract():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    d = _run([sys.executable, "-W", "ignore", "bench.py", "--gaussians", "8000", "--steps", "2", "--warmup", "1", "--cpu-sample-rays", "100000"])
+    d = _run([sys.executable, "-W", "ignore", "bench.py", "--gaussians", "8000", "--steps", "2", "--warmup", "1", "--cpu-sample-rays", "100000", "--full"])
     assert REQUIRED <= set(d) and "cpu_baseline" in d
     assert d["metric"] == "poses/sec" and d["unit"] == "poses/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["data"] == "synthetic"
@@ -96,17 +96,27 @@ def test_bench_plain_start_self_launches_the_ranks():
 
 
 @pytest.mark.timeout(900)
-def test_bench_pipelined_steps_give_the_poses_of_one_batch_at_a_time():
+def test_bench_pipelined_steps_give_the_poses_of_one_batch_at_a_time(tmp_path):
     """Round 5: two batches in flight (6dgs_amd.test.PoseStream: batch N + 1 submitted before batch N is collected, its image side on a second stream)
-    against --no-pipeline: the same poses BIT FOR BIT, the pipelining named in the line."""
+    against --no-pipeline: the same poses BIT FOR BIT, the pipelining named in the line.  --dump-outputs of both runs: the same arrays bit for bit,
+    the poses those of the line; the plain run (no --full) prints none of the secondary figures."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     args = ["bench.py", "--gaussians", "40000", "--steps", "4", "--warmup", "1", "--skip-cpu-baseline", "--skip-reference-mode", "--l32-steps", "0"]
-    a = _run([sys.executable, "-W", "ignore", *args], env={"SIXDGS_BENCH_DUMP_POSES": "1"})
-    b = _run([sys.executable, "-W", "ignore", *args, "--no-pipeline"], env={"SIXDGS_BENCH_DUMP_POSES": "1"})
+    da, db = str(tmp_path / "a"), str(tmp_path / "b")
+    a = _run([sys.executable, "-W", "ignore", *args, "--full", "--dump-outputs", da], env={"SIXDGS_BENCH_DUMP_POSES": "1"})
+    b = _run([sys.executable, "-W", "ignore", *args, "--no-pipeline", "--dump-outputs", db], env={"SIXDGS_BENCH_DUMP_POSES": "1"})
     assert a["config"]["pipeline"].startswith("2 batches in flight") and b["config"]["pipeline"].startswith("none")
     assert a["config"]["scoring_path"] == b["config"]["scoring_path"] == "select"
     assert a["poses_last_step"] == b["poses_last_step"] and len(a["poses_last_step"]) == 8
+    names = sorted(os.listdir(da))
+    assert names == sorted(os.listdir(db)) and {"c2w.npy", "topk_indices.npy", "topk_weights.npy", "up.npy"} <= set(names), names
+    for n in names:
+        xa, xb = np.load(os.path.join(da, n)), np.load(os.path.join(db, n))
+        assert xa.dtype in (np.float32, np.float64) and xa.dtype == xb.dtype and np.array_equal(xa, xb), n
+    assert np.array_equal(np.load(os.path.join(da, "c2w.npy")), np.asarray(a["poses_last_step"], np.float32))
+    assert np.load(os.path.join(da, "topk_indices.npy")).shape == (8, 100)
+    assert not {"roofline", "headline_b4", "reference_mode", "cpu_baseline", "fp32_logits_mode"} & set(b) and "roofline" in a
     assert a["median_step"]["n"] == b["median_step"]["n"] == 4 and "completions" in a["median_step"]["note"]
     assert a["headline_b4"]["images_per_gpu_per_step"] == 4 and a["headline_b4"]["value"] > 0 and "headline_b8" not in a      # the 4-image figure of rounds 1-5 beside it
     assert a["config"]["select_sweep_launches"] == [[8, 8]]                 # eight 256-token views: eight tiles, one launch
@@ -139,15 +149,15 @@ def test_bench_presets_cfg1_cfg2_and_streamed_scorer():
     small size."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    d = _run([sys.executable, "-W", "ignore", "bench.py", "--config", "cfg1", "--steps", "5", "--skip-cpu-baseline"])
+    d = _run([sys.executable, "-W", "ignore", "bench.py", "--config", "cfg1", "--steps", "5", "--skip-cpu-baseline", "--full"])
     assert d["config"]["preset"] == "cfg1" and d["config"]["gaussians"] == 10_000 and d["config"]["images_per_gpu_per_step"] == 1
     assert d["median_step"]["n"] == 5 and d["median_step"]["min_ms"] <= d["median_step"]["ms"] <= d["median_step"]["max_ms"]
     assert d["fp32_logits_mode"]["mma"] == "f16x3l32" and d["fp32_logits_mode"]["value"] > 0
     assert "traffic_source" in d["roofline"]
-    d = _run([sys.executable, "-W", "ignore", "bench.py", "--config", "cfg2", "--gaussians", "20000", "--steps", "2", "--skip-cpu-baseline"])
+    d = _run([sys.executable, "-W", "ignore", "bench.py", "--config", "cfg2", "--gaussians", "20000", "--steps", "2", "--skip-cpu-baseline", "--full"])
     assert d["config"]["preset"] == "cfg2" and "PLY" in d["config"]["workload"] and d["config"]["images_per_gpu_per_step"] == 1
     d = _run([sys.executable, "-W", "ignore", "bench.py", "--config", "cfg4", "--gaussians", "4000", "--batch", "3", "--chunk-rays", "300000",
-              "--steps", "1", "--skip-cpu-baseline"])
+              "--steps", "1", "--skip-cpu-baseline", "--full"])
     assert d["config"]["scoring"] == "streamed" and d["config"]["rays"] == 4000 * 256 and d["roofline"]["launches"] >= 8
 
 

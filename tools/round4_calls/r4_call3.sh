@@ -6,7 +6,7 @@ for a in abl2 abl18 abl27 abl59; do
   SIXDGS_LIB=$PWD/build/variants/lib_abl.so POWER_RAYS=16000000 timeout 150 python tools/power_trace.py $a 6 2>&1 | grep -E "^POWER" >> $O/power_ablation.log
 done
 cut -c1-330 $O/power_ablation.log
-(timeout 300 python bench.py --config cfg2 --steps 20 --warmup 3 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_cfg2.json 2> $O/bench_cfg2.err); python -c "import json;d=json.load(open('$O/bench_cfg2.json'));print('cfg2', d['value'], d['ms_per_step'], d['median_step'], d['roofline']['avg_launch_ms'])"
+(timeout 300 python bench.py --full --config cfg2 --steps 20 --warmup 3 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_cfg2.json 2> $O/bench_cfg2.err); python -c "import json;d=json.load(open('$O/bench_cfg2.json'));print('cfg2', d['value'], d['ms_per_step'], d['median_step'], d['roofline']['avg_launch_ms'])"
 (timeout 400 python bench.py --config cfg5-standin --scenes tt_ --skip-cpu-baseline > $O/bench_cfg5_tt.json 2> $O/bench_cfg5_tt.err); python - <<PY
 import json
 d=json.load(open("$O/bench_cfg5_tt.json"))

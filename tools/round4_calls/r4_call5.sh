@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 bash tools/validate_round4.sh r04v
 bash tools/profile_round4.sh r04p > gpurun_out/r04p_stdout.log 2>&1; tail -30 gpurun_out/r04p_stdout.log
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r04v
-(timeout 200 python bench.py --config cfg2 --graph --steps 20 --warmup 3 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_cfg2_graph.json 2> $O/bench_cfg2_graph.err); python -c "import json;d=json.load(open('$O/bench_cfg2_graph.json'));print('cfg2 graph', d['value'], d['ms_per_step'], d['median_step'])"
+(timeout 200 python bench.py --full --config cfg2 --graph --steps 20 --warmup 3 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_cfg2_graph.json 2> $O/bench_cfg2_graph.err); python -c "import json;d=json.load(open('$O/bench_cfg2_graph.json'));print('cfg2 graph', d['value'], d['ms_per_step'], d['median_step'])"
 (timeout 900 python bench.py --config cfg5-standin > $O/bench_cfg5_standin.json 2> $O/bench_cfg5_standin.err); python - <<PY
 import json
 d=json.load(open("$O/bench_cfg5_standin.json"))

@@ -9,7 +9,7 @@ print(d['scene_setup_breakdown_s_total'])
 for r in d['scenes']: print(r['scene'], r['rays'], r['scoring'], r['poses_per_s'], r['sweep_tflops'], r['tokens_per_image_mean'], r['setup_s'], r['setup_breakdown_s'])
 PY
 for C in cfg2 cfg3 cfg4; do
-  (timeout 600 python bench.py --config $C --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_$C.json 2> $O/bench_$C.err)
+  (timeout 600 python bench.py --full --config $C --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_$C.json 2> $O/bench_$C.err)
   python -c "
 import json;d=json.load(open('$O/bench_$C.json'));print('$C', d['value'],d['ms_per_step'],d['median_step']['ms'],d['roofline']['frac'],d['roofline']['avg_launch_ms'],d['scene_setup_s'].get('ray_mlp_keys_tflops'), d['config'].get('pipeline','')[:20])"
 done

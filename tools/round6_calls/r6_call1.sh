@@ -7,9 +7,9 @@ for st in 0 1 2 3 4; do python -W ignore tools/probe_alloc.py --stage $st; done 
 python -W ignore tools/probe_alloc.py --stage 0 --raw >> $O/probe_alloc.log 2>&1
 python -W ignore tools/probe_alloc.py --stage 4 --raw >> $O/probe_alloc.log 2>&1
 python -W ignore tools/probe_alloc.py --stage 0 --gb 49 >> $O/probe_alloc.log 2>&1
-python -W ignore bench.py --config cfg2 --steps 20 --skip-cpu-baseline > $O/bench_cfg2_a.json 2> $O/bench_cfg2_a.err
-python -W ignore bench.py --config cfg2 --steps 20 --skip-cpu-baseline > $O/bench_cfg2_b.json 2> $O/bench_cfg2_b.err
-python -W ignore bench.py --steps 20 --warmup 2 > $O/bench_default.json 2> $O/bench_default.err
+python -W ignore bench.py --full --config cfg2 --steps 20 --skip-cpu-baseline > $O/bench_cfg2_a.json 2> $O/bench_cfg2_a.err
+python -W ignore bench.py --full --config cfg2 --steps 20 --skip-cpu-baseline > $O/bench_cfg2_b.json 2> $O/bench_cfg2_b.err
+python -W ignore bench.py --full --steps 20 --warmup 2 > $O/bench_default.json 2> $O/bench_default.err
 tail -3 $O/select_arena.log $O/cfg5_full.log; cat $O/probe_alloc.log
 python - <<PY
 import json

@@ -4,9 +4,9 @@ export SIXDGS_RANDOM_BACKBONE=1
 cd $R
 ( time python -m pytest tests/test_gpu_backbone.py tests/test_gpu_e2e.py tests/test_gpu_cfg1.py -q -x 2>&1 | tail -n 25 ) > $O/tests.log 2>&1
 grep -E "passed|failed|Error|assert " $O/tests.log | head
-python -W ignore bench.py --mode reference --batch 16 --steps 20 --skip-cpu-baseline > $O/bench_refmode16.json 2> $O/bench_refmode16.err
-python -W ignore bench.py --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python -W ignore bench.py --steps 10 --warmup 2 --skip-cpu-baseline --l32-steps 0 > $O/bench_headline.json 2> $O/bench_headline.err
+python -W ignore bench.py --full --mode reference --batch 16 --steps 20 --skip-cpu-baseline > $O/bench_refmode16.json 2> $O/bench_refmode16.err
+python -W ignore bench.py --full --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python -W ignore bench.py --full --steps 10 --warmup 2 --skip-cpu-baseline --l32-steps 0 > $O/bench_headline.json 2> $O/bench_headline.err
 python - <<PY
 import json
 for n in ("refmode16","cfg2","headline"):

@@ -4,7 +4,7 @@ export SIXDGS_RANDOM_BACKBONE=1
 python -W ignore tools/probe_cumask.py > $O/probe_cumask.log 2>&1
 ( time python -m pytest tests/test_gpu_select.py -q -x 2>&1 | tail -8 ) > $O/select_tests.log 2>&1
 ( time python -m pytest tests/test_gpu_e2e.py tests/test_gpu_bench_contract.py -q -x -k "streamed or pipelined" 2>&1 | tail -8 ) > $O/pipeline_tests.log 2>&1
-B="python -W ignore bench.py --steps 20 --warmup 2 --skip-cpu-baseline --skip-reference-mode --l32-steps 0"
+B="python -W ignore bench.py --full --steps 20 --warmup 2 --skip-cpu-baseline --skip-reference-mode --l32-steps 0"
 run() { # name, env...
   n=$1; shift
   env "$@" SIXDGS_BENCH_DUMP_POSES=1 $B > $O/bench_$n.json 2> $O/bench_$n.err

@@ -2,11 +2,11 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06c21; mkdir -p $O
 export SIXDGS_RANDOM_BACKBONE=1
 cd $R
-python -W ignore bench.py --mode reference --batch 16 --steps 20 --skip-cpu-baseline > $O/bench_refmode16.json 2> $O/bench_refmode16.err
-python -W ignore bench.py --mode reference --batch 16 --steps 20 --skip-cpu-baseline --no-pipeline > $O/bench_refmode16_nopipe.json 2> $O/bench_refmode16_nopipe.err
-python -W ignore bench.py --mode reference --steps 20 --skip-cpu-baseline > $O/bench_refmode4.json 2> $O/bench_refmode4.err
-python -W ignore bench.py --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python -W ignore bench.py > $O/bench_default.json 2> $O/bench_default.err
+python -W ignore bench.py --full --mode reference --batch 16 --steps 20 --skip-cpu-baseline > $O/bench_refmode16.json 2> $O/bench_refmode16.err
+python -W ignore bench.py --full --mode reference --batch 16 --steps 20 --skip-cpu-baseline --no-pipeline > $O/bench_refmode16_nopipe.json 2> $O/bench_refmode16_nopipe.err
+python -W ignore bench.py --full --mode reference --steps 20 --skip-cpu-baseline > $O/bench_refmode4.json 2> $O/bench_refmode4.err
+python -W ignore bench.py --full --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python -W ignore bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python - <<PY
 import json
 for n in ("refmode16","refmode16_nopipe","refmode4","cfg2","default"):

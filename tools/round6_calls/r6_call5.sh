@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT; O=$GRAFT_REPO_ROOT/gpurun_out/r06c5; mkdir -p $O
 export SIXDGS_RANDOM_BACKBONE=1
 ( time python -m pytest tests/test_gpu_e2e.py tests/test_gpu_bench_contract.py tests/test_gpu_select.py -q -x -k "streamed or pipelined or tail_on" 2>&1 | tail -n 8 ) > $O/pipeline_tests.log 2>&1
-B="python -W ignore bench.py --steps 20 --warmup 2 --skip-cpu-baseline --skip-reference-mode --l32-steps 0"
+B="python -W ignore bench.py --full --steps 20 --warmup 2 --skip-cpu-baseline --skip-reference-mode --l32-steps 0"
 run() { n=$1; shift; env "$@" SIXDGS_BENCH_DUMP_POSES=1 $B > $O/bench_$n.json 2> $O/bench_$n.err; }
 for rep in 1 2 3; do
   run r5order_$rep SIXDGS_POSE_STREAM_LEAD=0
@@ -10,10 +10,10 @@ for rep in 1 2 3; do
 done
 run lead_tail SIXDGS_POSE_STREAM_LEAD=1 SIXDGS_POSE_STREAM_TAIL=1
 env SIXDGS_BENCH_DUMP_POSES=1 $B --no-pipeline --b8-steps 0 > $O/bench_nopipe.json 2> $O/bench_nopipe.err
-python -W ignore bench.py --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2_lead.json 2> $O/bench_cfg2_lead.err
-SIXDGS_POSE_STREAM_LEAD=0 python -W ignore bench.py --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2_r5order.json 2> $O/bench_cfg2_r5order.err
-python -W ignore bench.py --config cfg3 --steps 6 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_cfg3_lead.json 2> $O/bench_cfg3_lead.err
-SIXDGS_POSE_STREAM_LEAD=0 python -W ignore bench.py --config cfg3 --steps 6 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_cfg3_r5order.json 2> $O/bench_cfg3_r5order.err
+python -W ignore bench.py --full --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2_lead.json 2> $O/bench_cfg2_lead.err
+SIXDGS_POSE_STREAM_LEAD=0 python -W ignore bench.py --full --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2_r5order.json 2> $O/bench_cfg2_r5order.err
+python -W ignore bench.py --full --config cfg3 --steps 6 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_cfg3_lead.json 2> $O/bench_cfg3_lead.err
+SIXDGS_POSE_STREAM_LEAD=0 python -W ignore bench.py --full --config cfg3 --steps 6 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 > $O/bench_cfg3_r5order.json 2> $O/bench_cfg3_r5order.err
 python - <<PY
 import json, glob
 import numpy as np

@@ -6,7 +6,7 @@ cd $R
 grep -E "passed|failed|Error|assert " $O/tests.log | head
 for rep in 1 2; do for v in 3 1; do for c in "headline --batch 8" "headline --batch 4" cfg2 cfg3; do
   n=$(echo $c | tr -d ' -'); st=10; [ "$c" = cfg2 ] && st=40; [ "$c" = cfg3 ] && st=5
-  SIXDGS_PREPASS_TERMS=$v python -W ignore bench.py --config $c --steps $st --warmup 2 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 --b8-steps 0 > $O/bench_t${v}_${n}_$rep.json 2> $O/bench_t${v}_${n}_$rep.err
+  SIXDGS_PREPASS_TERMS=$v python -W ignore bench.py --full --config $c --steps $st --warmup 2 --skip-cpu-baseline --skip-reference-mode --l32-steps 0 --b8-steps 0 > $O/bench_t${v}_${n}_$rep.json 2> $O/bench_t${v}_${n}_$rep.err
   python -c "
 import json;d=json.loads([l for l in open('$O/bench_t${v}_${n}_$rep.json') if l.startswith('{')][-1]);print('terms $v $n run $rep:',d['value'],d['ms_per_step'],d['median_step']['ms'],d['roofline']['avg_launch_ms'],round(d['ms_per_step']-d['roofline']['avg_launch_ms']*len(d['config']['select_sweep_launches']),3),d['config'].get('select_candidates_last_batch'))" || tail -5 $O/bench_t${v}_${n}_$rep.err
 done; done; done

@@ -6,8 +6,8 @@ tail -n 12 $O/backbone_tests.log
 python -W ignore tools/time_vit_gemms.py > $O/vit_gemms.md 2> $O/vit_gemms.err
 cat $O/vit_gemms.md; tail -n 5 $O/vit_gemms.err
 for v in 0 1; do
-  SIXDGS_VIT_FUSED=$v python -W ignore bench.py --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2_fused$v.json 2> $O/bench_cfg2_fused$v.err
-  SIXDGS_VIT_FUSED=$v python -W ignore bench.py --mode reference --batch 16 --steps 20 --skip-cpu-baseline > $O/bench_refmode16_fused$v.json 2> $O/bench_refmode16_fused$v.err
+  SIXDGS_VIT_FUSED=$v python -W ignore bench.py --full --config cfg2 --steps 30 --skip-cpu-baseline > $O/bench_cfg2_fused$v.json 2> $O/bench_cfg2_fused$v.err
+  SIXDGS_VIT_FUSED=$v python -W ignore bench.py --full --mode reference --batch 16 --steps 20 --skip-cpu-baseline > $O/bench_refmode16_fused$v.json 2> $O/bench_refmode16_fused$v.err
 done
 python - <<PY
 import json
