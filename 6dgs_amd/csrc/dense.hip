@@ -55,30 +55,16 @@ __device__ __forceinline__ float pow2i(int e) { return __uint_as_float((unsigned
 // lines at the same time) while the layer's weight planes are re-read from it for every tile.  Alternating processes on one box, 8 M rays (profiles/
 // r06_chain_nt_ab.log): 365.3 -> 369.9 TFLOP/s with both hints (loads alone 368.9, stores alone 365.1 -- round 2's "non-temporal output stores: no change"
 // stands on its own); L2 <-> fabric bytes unchanged (FETCH_SIZE +2 %, WRITE_SIZE the same): what improves is the weight planes' stay in L2, not the traffic.
-// Same keys bit for bit (cache hints).  -DSDG_ACT_NT=0 -DSDG_OUT_NT=0: the accesses of rounds 2-5.
-#ifndef SDG_ACT_NT
-#define SDG_ACT_NT 1
-#endif
+// Same keys bit for bit (cache hints).
 typedef unsigned dense_u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld_act(const char* p) {
-#if SDG_ACT_NT
   const dense_u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const dense_u32x4_t*>(p));
   return uint4{v.x, v.y, v.z, v.w};
-#else
-  return *reinterpret_cast<const uint4*>(p);
-#endif
 }
 
-#ifndef SDG_OUT_NT
-#define SDG_OUT_NT 1
-#endif
 typedef float dense_f32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st_act(char* p, float a, float b, float c, float d) {
-#if SDG_OUT_NT
   __builtin_nontemporal_store(dense_f32x4_t{a, b, c, d}, reinterpret_cast<dense_f32x4_t*>(p));
-#else
-  *reinterpret_cast<float4*>(p) = float4{a, b, c, d};
-#endif
 }
 
 struct DenseArgs {
@@ -346,20 +332,6 @@ __global__ void __launch_bounds__(512, 1) k_dense_planes(DenseArgs A, unsigned n
         }
       }
     }
-#ifdef SDG_FUSE_L1_PROBE
-    // Timing probe (developer build, profiles/r06_chain_l1_fused_probe.md): the MATRIX WORK a loader that recomputes h1 = ReLU(W1 x) would add to a layer-2 pass -- per
-    // slab of 32 h1 features 32 x 256 rays x 160 inputs x 3 terms = 240 MFMAs per workgroup, 30 per wave -- issued here on a zero weight fragment (the sums, hence the keys,
-    // are unchanged), for the 16-slab layer only.  Everything else such a loader needs (x streamed 16 x from L2, 64 more accumulators, the block scale of h1) is NOT in it.
-    if (NTM == 2 && NTN == 4 && ks == 16) {
-      f16x8_t z;
-#pragma unroll
-      for (int e_ = 0; e_ < 8; ++e_) z[e_] = (_Float16)0.f;
-      asm volatile("" : "+v"(z));
-      const f16x8_t bz = *reinterpret_cast<const f16x8_t*>(smem + buf * kWStage + (FP + wn * 32 * NTN + frow) * kPRow + fk);
-#pragma unroll
-      for (int i_ = 0; i_ < 30; ++i_) acc[i_ & 1][(i_ >> 1) & 3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(z, bz, acc[i_ & 1][(i_ >> 1) & 3], 0, 0, 0);
-    }
-#endif
     SDG_ADVANCE()
     SDG_T(t1_)
     SDG_ACC(0, t0_, t1_)

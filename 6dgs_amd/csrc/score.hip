@@ -157,10 +157,12 @@ struct LogitsF16Args {
 constexpr int kOutF32 = 0;     // logits as fp32 (blocked layout) + running (max, sumexp)
 constexpr int kOutL24 = 1;     // logits as 24-bit fixed point + running (max, sumexp)
 constexpr int kOutStats = 2;   // running (max, sumexp) only (the sample pre-pass of the select path)
-constexpr int kAblOneTerm = 8192;   // ABL bit (a product mode, not an ablation): only the h*h term of the three -- logits to ~2^-11 of |q||k| / sqrt(384).  For the sample
-                                    // pre-pass alone: its (max, sumexp) set the exponent offsets ref_t and the scale Z~_t of the sweep, whose g_t = Z_t / (f Z~_t) is EXACT
-                                    // relative to whatever Z~_t it was given -- the pre-pass decides how wide the bounds are, never the answer (include/sixdgs.h)
 constexpr int kOutUB = 3;      // per ray: sum_t exp(l_tr - ref_t) / (f Z~_t) (4 token-quarter partials); per token: the exact sum over rays
+// which of the three MFMA terms (l*h, h*l, h*h) the kernel issues
+constexpr int kAllTerms = 3;
+constexpr int kOneTerm = 1;    // only the h*h term -- logits to ~2^-11 of |q||k| / sqrt(384).  For the sample pre-pass alone: its (max, sumexp) set the
+                               // exponent offsets ref_t and the scale Z~_t of the sweep, whose g_t = Z_t / (f Z~_t) is EXACT relative to whatever Z~_t it
+                               // was given -- the pre-pass decides how wide the bounds are, never the answer (include/sixdgs.h)
 
 // A wave-uniform global load through the scalar cache.  As a plain load hipcc emits global_load_dword (the kernel also
 // stores to global memory, so it cannot prove the location unclobbered) followed by s_waitcnt vmcnt(0) -- which drains
@@ -175,12 +177,9 @@ __device__ __forceinline__ f16x8 lds_read_frag_h_off(unsigned addr, const int im
   return v;
 }
 
-#ifdef SIXDGS_ABLATION
-__device__ unsigned long long g_dbg_cycles[8][8];   // [wave][phase] summed over the blocks with grp == 0 (timing variant)
-#endif
 // ------------------------------------------------------------------------------------------------
 // fp16x3 logits kernel, 256 tokens x 256 rays per tile, one workgroup of 8 waves per CU.
-// How it got this shape (all measured on MI355X, tools/ablate_logits.py; DESIGN.md section 3b has the numbers):
+// How it got this shape (all measured on MI355X with the ablation build, since retired; DESIGN.md section 3b has the numbers):
 //  * 128 x 128 tiles / 4 waves (the bf16x6 structure): every non-MFMA cycle is exposed with one wave per SIMD;
 //  * the reference orientation Q K^T leaves a lane with one ray column and 16 token rows: 64 four-byte stores per lane
 //    and two 31-step cross-lane reductions per tile for the row statistics.  Computing K Q^T instead gives a lane ONE
@@ -232,12 +231,13 @@ constexpr int kQStageX = 256 * 64;       // one plane of one stage
 constexpr int kKBaseX = 4 * kQStageX;    // 64 KiB
 constexpr int kLdsX = kKBaseX + 6 * kQStageX;   // 160 KiB
 
-// OUT: what leaves the kernel (kOut*): fp32 or 24-bit fixed-point logits (see kTileBytes24), statistics only, or the
-// upper-bound column sums of the select path
-template <int ABL, int OUT, bool PERS = false>
+// TERMS: kAllTerms or kOneTerm.  OUT: what leaves the kernel (kOut*): fp32 or 24-bit fixed-point logits (see kTileBytes24),
+// statistics only, or the upper-bound column sums of the select path
+template <int TERMS, int OUT, bool PERS = false>
 __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
+  static_assert(TERMS == kAllTerms || TERMS == kOneTerm, "k_logits_f16x: TERMS is 3 or 1");
   constexpr bool L24 = OUT == kOutL24;
-  constexpr bool kOneTerm = (ABL & kAblOneTerm) != 0;
+  constexpr bool one_term = TERMS == kOneTerm;
   __shared__ __attribute__((aligned(1024))) char lds[kLdsX];
   const unsigned w = xcd_remap(blockIdx.x, gridDim.x);
   const int bl = (int)(w % (unsigned)A.nb);
@@ -297,20 +297,15 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
     // sibling set, which meet after every tile -- all its readers pass within a tile's time -- while the q planes of the launch's slots are re-read for every
     // tile by every set of the XCD.  With 8 slots those q planes are 3.1 MB of the XCD's 4 MB L2, and key lines without the hint displaced them: L2 <-> fabric
     // traffic 1.44 x the algorithmic bytes at 8 tiles per launch; with it 1.02 x, the sweep the same or 0.2 % faster (profiles/r06_key_stream_nt.md; rounds
-    // 2-4 measured the hint at 2-4 slots per launch, where the q planes fit anyway: no difference, as again now).  -DSDG_KEY_AUX=0: the loads of rounds 1-5.
-#ifndef SDG_KEY_AUX
-#define SDG_KEY_AUX 2
-#endif
+    // 2-4 measured the hint at 2-4 slots per launch, where the q planes fit anyway: no difference, as again now).
     auto issue_q = [&](const int s, const int qstage, const int i) {
-      if (ABL & 1) return;
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(qbase + (offQ[i] + (unsigned)(s * kSlabF))),
                                        (lds_ptr_t)(lds + qstage * (2 * kQStageX) + (wave * 4 + i) * 1024), 16, 0, 0);
     };
     auto issue_k = [&](const char* kbase, int lim, const int s, const int kstage, const int i) {
-      if (ABL & 8) return;
       const unsigned ob = (unsigned)min(rowK[i], lim) * kRowF + offK[i] + (unsigned)(s * kSlabF);
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(kbase + ob),
-                                       (lds_ptr_t)(lds + kKBaseX + kstage * (2 * kQStageX) + (wave * 4 + i) * 1024), 16, 0, SDG_KEY_AUX);
+                                       (lds_ptr_t)(lds + kKBaseX + kstage * (2 * kQStageX) + (wave * 4 + i) * 1024), 16, 0, 2);
     };
     auto tile_lim = [&](int tile) {
       const int64_t left = A.r - (int64_t)tile * kBNX - 1;
@@ -347,15 +342,6 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
     };
-    // timing variant (ABL & 2048): phase p accumulates the cycles since the previous stamp (0 loop overhead, 1 steps 0-2,
-    // 2 vmcnt wait, 3 barrier, 4 step 3, 5 epilogue)
-    unsigned long long t_prev = 0, t_acc[6] = {0, 0, 0, 0, 0, 0};
-    auto tstamp = [&](const int ph) {
-      const unsigned long long now = __builtin_readcyclecounter();
-      t_acc[ph] += now - t_prev;
-      t_prev = now;
-    };
-    if (ABL & 2048) t_prev = __builtin_readcyclecounter();
     // ---- prologue: key slabs 0, 1, 2 and q slabs 0, 1 in the steady-state order (q of a batch before its key) ----------
 #pragma unroll
     for (int i = 0; i < 4; ++i) issue_k(kcur, lim_cur, 0, 0, i);
@@ -373,21 +359,11 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int pl = 0; pl < 2; ++pl) {
-        if (kOneTerm && pl == 1) continue;      // (a fragment read whose result is never used must not be issued: its register is free for reuse before the data lands)
+        if (one_term && pl == 1) continue;      // (a fragment read whose result is never used must not be issued: its register is free for reuse before the data lands)
         a0[t][pl] = read_a(t, 0, pl, 0);
         b0[t][pl] = read_b(t, 0, pl, 0);
       }
     wait_lds();
-    if (ABL & 16) {      // (ablation "no fragment reads": the second fragment set must still be DEFINED, or the compiler drops the MFMAs that use it --
-#pragma unroll          //  the r1-r4 "MFMA only" figures above 2.5 PFLOP/s came from that)
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-          a1[t][pl] = a0[t][pl];
-          b1[t][pl] = b0[t][pl];
-          asm volatile("" : "+v"(a1[t][pl]), "+v"(b1[t][pl]));
-        }
-    }
 
     for (int tile = t_begin; tile < t_end; ++tile) {
       // after the last tile of the run the prefetch simply re-reads the current tile (harmless, keeps the slab loop and
@@ -402,7 +378,7 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
       // does its share of the workgroup's data movement -- per slab the same counted wait, the same barrier and the same 8 DMA pieces in the same
       // order as the waves that compute (vmcnt bookkeeping unchanged), issued right behind the barrier.  Wave-uniform branch; waves 0-3 (token rows
       // 0-127) sit on the four SIMDs, so an image of <= 128 tokens leaves every SIMD with ONE computing wave and half the matrix work.
-      if (!active && !(ABL & 4096)) {
+      if (!active) {
         int ks3 = 0;                                 // sl % 3 (a ROLLED loop with run-time stages: unrolled, its 96 piece addresses cost the computing
 #pragma unroll 1                                     // waves registers -- 41 spilled VGPRs in the first build)
         for (int sl = 0; sl < 12; ++sl) {
@@ -441,7 +417,7 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
 #pragma unroll
           for (int z = 0; z < 4; ++z) {
             const int tm = z >> 1, tn = z & 1;
-            if (!(ABL & 4) && !((ABL & kAblOneTerm) && q < 2))
+            if (!(one_term && q < 2))
               acc[tm][2 * h + tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xb[tn][PB[q]], xa[tm][PA[q]], acc[tm][2 * h + tn], 0, 0, 0);
             side(q * 4 + z);
             __builtin_amdgcn_sched_barrier(0);
@@ -453,38 +429,34 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
       for (int sl = 0; sl < 12; ++sl) {
         const int qs = sl & 1, ks3 = sl % 3;              // stages of this slab
         const int qn = (sl + 1) & 1, kn = (sl + 1) % 3;    // stages of the next slab
-        if (ABL & 2048) tstamp(0);
         // step 0: (k-step 0, ray half 0); read B(k-step 0, half 1)
         mfma_step(a0, b0, 0, [&](const int slot) {
-          if (kOneTerm && (slot & 1)) return;
-          if (!(ABL & 16) && slot < 4) b1[slot >> 1][slot & 1] = read_b(2 + (slot >> 1), 0, slot & 1, ks3);
+          if (one_term && (slot & 1)) return;
+          if (slot < 4) b1[slot >> 1][slot & 1] = read_b(2 + (slot >> 1), 0, slot & 1, ks3);
         });
         wait_lds();
         // step 1: (k-step 0, half 1); read A(k-step 1), B(k-step 1, half 0)
         mfma_step(a0, b1, 1, [&](const int slot) {
-          if (kOneTerm && (slot & 1)) return;
-          if (!(ABL & 16) && slot < 4) a1[slot >> 1][slot & 1] = read_a(slot >> 1, 1, slot & 1, qs);
-          else if (!(ABL & 16) && slot < 8) b0[(slot - 4) >> 1][slot & 1] = read_b((slot - 4) >> 1, 1, slot & 1, ks3);
+          if (one_term && (slot & 1)) return;
+          if (slot < 4) a1[slot >> 1][slot & 1] = read_a(slot >> 1, 1, slot & 1, qs);
+          else if (slot < 8) b0[(slot - 4) >> 1][slot & 1] = read_b((slot - 4) >> 1, 1, slot & 1, ks3);
         });
         wait_lds();
         // step 2: (k-step 1, half 0); read B(k-step 1, half 1) -- the last reads of this slab
         mfma_step(a1, b0, 0, [&](const int slot) {
-          if (kOneTerm && (slot & 1)) return;
-          if (!(ABL & 16) && slot < 4) b1[slot >> 1][slot & 1] = read_b(2 + (slot >> 1), 1, slot & 1, ks3);
+          if (one_term && (slot & 1)) return;
+          if (slot < 4) b1[slot >> 1][slot & 1] = read_b(2 + (slot >> 1), 1, slot & 1, ks3);
         });
         wait_lds();
         // q(sl+1) was issued first in the previous batch: only that batch's 4 key pieces are younger.  After the barrier
         // slab sl+1 is visible to every wave and the stages of slab sl are free.
-        if (ABL & 2048) tstamp(1);
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        if (ABL & 2048) tstamp(2);
-        if (!(ABL & 32)) __builtin_amdgcn_s_barrier();
-        if (ABL & 2048) tstamp(3);
+        __builtin_amdgcn_s_barrier();
         // step 3: (k-step 1, half 1); read A / B(half 0) of slab sl+1; issue q(sl+2) -> q stage qs, key(sl+3) -> key stage ks3
         mfma_step(a1, b1, 1, [&](const int slot) {
-          if (!(kOneTerm && (slot & 1))) {
-            if (!(ABL & 16) && slot < 4) a0[slot >> 1][slot & 1] = read_a(slot >> 1, 0, slot & 1, qn);
-            else if (!(ABL & 16) && slot < 8) b0[(slot - 4) >> 1][slot & 1] = read_b((slot - 4) >> 1, 0, slot & 1, kn);
+          if (!(one_term && (slot & 1))) {
+            if (slot < 4) a0[slot >> 1][slot & 1] = read_a(slot >> 1, 0, slot & 1, qn);
+            else if (slot < 8) b0[(slot - 4) >> 1][slot & 1] = read_b((slot - 4) >> 1, 0, slot & 1, kn);
           }
           if (slot < 4) issue_q((sl + 2) % 12, qs, slot);
           else if (slot < 8) {
@@ -493,7 +465,6 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
           }
         });
         wait_lds();
-        if (ABL & 2048) tstamp(4);
       }
 
       // ---- sibling lock-step: the nb workgroups of this sibling set (same XCD: consecutive work items of the remap) meet here after
@@ -522,19 +493,6 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
           }
         }
       }
-      if (ABL & 2) {
-        float sacc = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc += acc[i][j][r];
-        if (sacc == 12345.678f) lg[lane] = sacc;
-        kcur = knext;
-        lim_cur = lim_next;
-        continue;
-      }
       // ---- epilogue.  Lane l holds token (l & 31) and, per accumulator register group rg, the four consecutive rays
       // 8 rg + 4 (l >> 5) + {0..3} of its 32-ray block: one 16-byte store per group, 1 KiB contiguous per wave instruction.
       // The constant undoes both power-of-two operand scales (exactly) and applies 1/sqrt 384.
@@ -548,12 +506,7 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
           const int t128 = min(2 * tile + wn, n_tiles128 - 1);
           const float cfl = ((cq * load_uniform(A.kinv + t128)) * kInvSqrtD) * 1.4426950408889634f;
           const bool ragged = lim_cur < kBNX - 1;
-#ifdef SDG_UB_OPAQUE
-          int ray0 = wn * 128 + 4 * (lane >> 5);
-          asm volatile("" : "+v"(ray0));        // formed here, not hoisted (see the two-pass branch below)
-#else
           const int ray0 = wn * 128 + 4 * (lane >> 5);
-#endif
           const bool lb0 = lane & 1, lb1 = lane & 2, lb2 = lane & 4, lb3 = lane & 8, lb4 = lane & 16;
           float fin[4];
 #pragma unroll
@@ -635,13 +588,13 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
               acc[tm][tn][4 * rg + 1] = v.y;
               acc[tm][tn][4 * rg + 2] = v.z;
               acc[tm][tn][4 * rg + 3] = v.w;
-              if (OUT == kOutF32 && !(ABL & 64)) {
+              if (OUT == kOutF32) {
                 typedef float f32x4 __attribute__((ext_vector_type(4)));
                 __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(tb + tm * 4096 + tn * 1024 + rg * 256));
               }
               mx = fmaxf(mx, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));   // clamped duplicate rays cannot raise the max
             }
-          if (L24 && !(ABL & 64)) {
+          if (L24) {
             // 24-bit fixed point of (this lane's tile maximum - logit), resolution 2^-19, clamped at 32 (e^-32 of the
             // largest term): an absolute error <= 2^-20 per logit, below the fp32 rounding of a logit of magnitude >= 16
             typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
@@ -684,16 +637,8 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
       }
       kcur = knext;
       lim_cur = lim_next;
-      if (ABL & 2048) tstamp(5);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the trailing prefetch
-#ifdef SIXDGS_ABLATION
-    if ((ABL & 2048) && lane == 0 && grp < 64) {
-#pragma unroll
-      for (int ph = 0; ph < 6; ++ph) atomicAdd(&g_dbg_cycles[wave][ph], t_acc[ph]);
-      if (wave == 0) atomicAdd(&g_dbg_cycles[0][7], 1ull);
-    }
-#endif
   }
   // merge the four partials of every token (2 ray halves of the lane layout x 2 waves wn) through the (now idle) ring
   __syncthreads();
@@ -1926,18 +1871,7 @@ int score_impl(int phase, bool planes, const float* q, const int32_t* d_n_tok, c
           V.tiles_per_group = (int)sdg_cdiv(n_tiles_x, n_groups_x);
           V.n_tiles = n_tiles_x;
           V.n_groups = n_groups_used;
-          auto kern = logits24 ? k_logits_f16x<0, kOutL24> : k_logits_f16x<0, kOutF32>;
-#ifdef SIXDGS_ABLATION   // timing experiments only (tools/ablate_logits.py builds a private copy of the library with it)
-          if (const char* ab = getenv("SIXDGS_DEBUG_ABLATE")) {
-#define SDG_ABL_CASE(n) case n: kern = logits24 ? k_logits_f16x<n, kOutL24> : k_logits_f16x<n, kOutF32>; break;
-            switch (atoi(ab)) {
-              SDG_ABL_CASE(1) SDG_ABL_CASE(8) SDG_ABL_CASE(9) SDG_ABL_CASE(2) SDG_ABL_CASE(11) SDG_ABL_CASE(27) SDG_ABL_CASE(59)
-              SDG_ABL_CASE(64) SDG_ABL_CASE(2048)
-              default: break;
-            }
-#undef SDG_ABL_CASE
-          }
-#endif
+          auto kern = logits24 ? k_logits_f16x<kAllTerms, kOutL24> : k_logits_f16x<kAllTerms, kOutF32>;
           hipLaunchKernelGGL(kern, dim3((unsigned)(n_groups_used * nb)), dim3(512), 0, s, V);
         } else if (mma_mode == SIXDGS_MMA_F32) {
           hipLaunchKernelGGL(k_logits<kMmaF32>, dim3((unsigned)(p.n_groups * 2), (unsigned)nb), dim3(256), 0, s, A);
@@ -2010,17 +1944,6 @@ int sixdgs_score_topk(const float* q, const int32_t* d_n_tok, int batch, const f
   return sixdgs_score_topk_ex(q, d_n_tok, nullptr, batch, key, nullptr, nullptr, r, topk, scores, idx, val, row_stats, ws, ws_bytes,
                               stream, nullptr, SIXDGS_MMA_DEFAULT);
 }
-
-#ifdef SIXDGS_ABLATION
-int sixdgs_debug_cycles(unsigned long long* host64, int reset) {   // ablation builds only (tools/ablate_logits.py)
-  hipError_t e = hipMemcpyFromSymbol(host64, HIP_SYMBOL(g_dbg_cycles), sizeof(unsigned long long) * 64);
-  if (e == hipSuccess && reset) {
-    unsigned long long z[64] = {0};
-    e = hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_cycles), z, sizeof(z));
-  }
-  return (int)e;
-}
-#endif
 
 int sixdgs_profile_collect(sixdgs_profile* prof, double* ms_total, double* flops_total, double* bytes_total, int* launches) {
   SDG_CHECK_ARG(prof);
@@ -2187,7 +2110,7 @@ static int sweep_slot_cap() {
   return cap;
 }
 
-// The sample pre-pass with ONE of the three MFMA terms (kAblOneTerm) -- for every launch, whatever its slot count: an image's statistics, candidates and
+// The sample pre-pass with ONE of the three MFMA terms (kOneTerm) -- for every launch, whatever its slot count: an image's statistics, candidates and
 // values must not depend on what it was batched with (test_token_packing_is_invisible..., test_sweep_launch_grouping_is_invisible).
 // SIXDGS_PREPASS_TERMS=3: all three (rounds 2-5).
 static bool prepass_one_term(int /*n_slots*/) {
@@ -2237,11 +2160,11 @@ int sixdgs_select_sample_stats(const float* q, const int32_t* d_n_tok, const int
         V.sib_sync = nullptr;
         V.sib_extra = 0u;
         V.sib_period = kSibPeriod;
-        if (prepass_one_term(T.n_slots)) hipLaunchKernelGGL((k_logits_f16x<kAblOneTerm, kOutStats, true>), dim3((unsigned)(V.n_sets * T.n_slots)), dim3(512), 0, s, V);
-        else hipLaunchKernelGGL((k_logits_f16x<0, kOutStats, true>), dim3((unsigned)(V.n_sets * T.n_slots)), dim3(512), 0, s, V);
+        if (prepass_one_term(T.n_slots)) hipLaunchKernelGGL((k_logits_f16x<kOneTerm, kOutStats, true>), dim3((unsigned)(V.n_sets * T.n_slots)), dim3(512), 0, s, V);
+        else hipLaunchKernelGGL((k_logits_f16x<kAllTerms, kOutStats, true>), dim3((unsigned)(V.n_sets * T.n_slots)), dim3(512), 0, s, V);
       } else {
-        if (prepass_one_term(T.n_slots)) hipLaunchKernelGGL((k_logits_f16x<kAblOneTerm, kOutStats>), dim3((unsigned)(V.n_groups * T.n_slots)), dim3(512), 0, s, V);
-        else hipLaunchKernelGGL((k_logits_f16x<0, kOutStats>), dim3((unsigned)(V.n_groups * T.n_slots)), dim3(512), 0, s, V);
+        if (prepass_one_term(T.n_slots)) hipLaunchKernelGGL((k_logits_f16x<kOneTerm, kOutStats>), dim3((unsigned)(V.n_groups * T.n_slots)), dim3(512), 0, s, V);
+        else hipLaunchKernelGGL((k_logits_f16x<kAllTerms, kOutStats>), dim3((unsigned)(V.n_groups * T.n_slots)), dim3(512), 0, s, V);
       }
     }
     hipLaunchKernelGGL(k_merge_stats_slots, dim3((unsigned)T.n_images, 4), dim3(1024), 0, s, w.partial, n_groups, T, row_stats, (float*)nullptr);
@@ -2319,17 +2242,7 @@ int sixdgs_select_sweep(const float* q, const int32_t* d_n_tok, const int32_t* h
         grid = (unsigned)(V.n_sets * ns);
       }
       SdgProfileScope scope(prof, s, 2.0 * tok * SIXDGS_D * (double)r, (double)r * (kRowF + T.n_images * 16.0));
-      auto kern = V.n_sets > 0 ? k_logits_f16x<0, kOutUB, true> : k_logits_f16x<0, kOutUB, false>;
-#ifdef SIXDGS_ABLATION   // timing / power experiments only (tools/power_trace.py abl<N> on a private -DSIXDGS_ABLATION build): the sweep with parts compiled out
-      if (const char* ab = getenv("SIXDGS_DEBUG_ABLATE")) {
-#define SDG_ABL_CASE(n) case n: kern = V.n_sets > 0 ? k_logits_f16x<n, kOutUB, true> : k_logits_f16x<n, kOutUB, false>; break;
-        switch (atoi(ab)) {
-          SDG_ABL_CASE(2) SDG_ABL_CASE(18) SDG_ABL_CASE(11) SDG_ABL_CASE(27) SDG_ABL_CASE(59) SDG_ABL_CASE(4096)
-          default: break;
-        }
-#undef SDG_ABL_CASE
-      }
-#endif
+      auto kern = V.n_sets > 0 ? k_logits_f16x<kAllTerms, kOutUB, true> : k_logits_f16x<kAllTerms, kOutUB, false>;
       hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, s, V);
     }
     hipLaunchKernelGGL(k_merge_stats_slots, dim3((unsigned)T.n_images, 4), dim3(1024), 0, s, w.partial, n_groups, T, (float*)nullptr, gsum);

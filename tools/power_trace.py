@@ -1,12 +1,8 @@
 """Socket power / shader clock sampled at >= 10 Hz while ONE kernel family runs in a loop (VERDICT r3 #4a: "power-bound" as a measurement).
 
-    python tools/power_trace.py <workload> [seconds]      workload = idle | sweep | chain | mfma | copy
+    python tools/power_trace.py <workload> [seconds]      workload = idle | sweep | chain | copy
       sweep : sixdgs_select_sweep (k_logits_f16x<kOutUB>), 4 images x 32 M rays of random key planes
       chain : sixdgs_ray_keys_ex (encode + five k_dense_planes launches per chunk), 8 M rays
-      mfma  : the sweep of an -DSIXDGS_ABLATION build with everything but its MFMAs compiled out (= abl59)
-      abl<N>: the sweep under compile-time ablation N (0 full, 2 no epilogue, 18 no fragment reads + no epilogue, 11 no DMA + no epilogue,
-              27 MFMA + barriers, 59 MFMA only; names in tools/ablate_logits.py)
-              (SIXDGS_LIB must point at build/variants/lib_abl.so: python tools/build_variant.py abl -DSIXDGS_ABLATION)
       copy  : torch copy of 8 GB (HBM only, no matrix pipe)
 
 The sampler is a separate PROCESS (amdsmi python bindings; sysfs hwmon as a fallback), so that the launch loop's host thread does not
@@ -113,8 +109,7 @@ def main():
         ops = importlib.import_module("6dgs_amd.ops")
         syn = importlib.import_module("6dgs_amd.synthetic")
         torch.manual_seed(0)
-        abl = 59 if wl == "mfma" else (int(wl[3:]) if wl.startswith("abl") else None)
-        if wl == "sweep" or abl is not None:
+        if wl == "sweep":
             B, R = 4, int(os.environ.get("POWER_RAYS", 32_000_000))
             planes = torch.empty(R, 1536, dtype=torch.uint8, device="cuda")
             scale = torch.empty((R + 127) // 128, device="cuda")
@@ -131,9 +126,6 @@ def main():
             ss = ops.SelectStream(q, nt, R, 100, 4096, [256] * B)
             ss.begin(sp, ssc)
             fl = 2.0 * 256 * 384 * R * B
-            if abl is not None:
-                os.environ["SIXDGS_DEBUG_ABLATE"] = str(abl)
-                note = f"select sweep k_logits_f16x<UB> under compile-time ablation {abl} (2 no epilogue, 18 no fragment reads + no epilogue, 11 no DMA + no epilogue, 27 MFMA + barriers, 59 MFMA only, 4096 idle-wave skip off)"
 
             def one():
                 ss.sweep(planes, scale, 0, None, update_norm=False)
