@@ -6,13 +6,16 @@ One torch.autograd.Function, `HipLinear`: y = act(x w^T + b) with all three prod
 (gemm.hip: 128x128 tiles, fp32 operands as 3 bf16 planes x 6 MFMA terms, fp32-equivalent):
 
     forward   y   = x  . w^T            [M,K] x [N,K] -> [M,N]     (bias + ReLU in the kernel's epilogue)
-    backward  dx  = dy . w              as dy [M,N] x (w^T) [K,N]   -> [M,K]   (when K is a multiple of 128: the kernel's N constraint)
+    backward  dx  = dy . w              as dy [M,N] x (w^T) [K,N]   -> [M,K]   (when K is a multiple of 128; N zero-padded to a
+                                                                                 multiple of 16: the kernel's K constraint)
               dw^T = x^T . dy           as x^T [K,M] x (dy^T) [N,M] -> [K,N]   (M zero-padded to a multiple of 16: the kernel's K constraint)
               db  = column sums of dy   (PyTorch reduction)
 
-The kernel wants K % 16 == 0 and N % 128 == 0, so the callers split / pad the reference's odd widths (141, 653, 398) with zeros --
-exact in value.  dx for a K that is not a multiple of 128 is only ever needed for inputs without gradient on this path (ray
-encodings, image tokens of a frozen backbone); if it is requested anyway it is formed by a PyTorch matmul, said so in the name.
+The kernel takes any M >= 0 and N > 0 but wants its contraction length K to be a multiple of 4, so the callers pad the
+reference's odd widths (141, 653, 398) to multiples of 16 with zeros -- exact in value.  dx for a K that is not a multiple of
+128 is only ever needed for inputs without gradient on this path (ray encodings, image tokens of a frozen backbone); if it is
+requested anyway it is formed by a PyTorch matmul, said so in the name.  With M = 0 every gradient is zero and no GEMM runs (dW
+would be a contraction of length 0, and an empty dy may carry any strides).
 """
 from __future__ import annotations
 
@@ -33,13 +36,23 @@ class HipLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if x.shape[0] == 0:         # no rows: zero gradients, no GEMM (the kernel rejects a contraction of length 0)
+            return (torch.zeros_like(x) if need[0] else None, torch.zeros_like(w) if need[1] else None,
+                    w.new_zeros(w.shape[0]) if ctx.has_bias and need[2] else None, None)
         dy = dy.contiguous()
         if ctx.relu:
             dy = dy * (y > 0)
         dx = dw = db = None
         m, k = x.shape
         if ctx.needs_input_grad[0]:
-            dx = ops.linear(dy, w.t().contiguous(), None, split_k=1) if k % 128 == 0 else dy @ w      # second form: PyTorch matmul (rocBLAS)
+            if k % 128 == 0:
+                dyp, wt, padn = dy, w.t().contiguous(), (-w.shape[0]) % 16
+                if padn:
+                    dyp, wt = F.pad(dy, (0, padn)), F.pad(wt, (0, padn))
+                dx = ops.linear(dyp, wt, None, split_k=1)
+            else:
+                dx = dy @ w                                              # PyTorch matmul (rocBLAS)
         if ctx.needs_input_grad[1]:
             pad = (-m) % 16
             xt, dyt = x.t().contiguous(), dy.t().contiguous()
