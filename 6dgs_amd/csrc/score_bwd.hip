@@ -1,0 +1,318 @@
+// score_bwd.hip -- backward of the scorer's softmax-over-rays column sum (training: ops.ray_attention_scores, the scorer of
+// IdentificationModule.forward_window).  For image b, with s[t][r] = q_t . k_r / sqrt(384), A[t][r] = softmax_r(s[t]),
+// score[r] = sum_t A[t][r] and g[r] = dL/dscore[r]:
+//
+//   c[t]  = sum_r A[t][r] g[r]
+//   dS    = A[t][r] (g[r] - c[t])
+//   dq_t  = sum_r dS[t][r] k_r / sqrt(384)
+//   dk_r  = sum_b sum_t dS[t][r] q_t / sqrt(384)
+//
+// Two kernels, neither with partial sums nor atomics (every sum has one owner and a fixed order: two calls give the same bits):
+//   k_bwd_q  one workgroup = 128 tokens of one image.  Sweep 1 over all rays forms the softmax sum and c (kept in the workspace for
+//            k_bwd_k), sweep 2
+//            recomputes the logits, forms dS and accumulates dq = dS . K in registers.  Two sweeps rather than one sweep of
+//            sum A g k and sum A k: their difference cancels where g is nearly constant over the rays that carry the mass.
+//   k_bwd_k  one workgroup = 128 rays.  Walks every 128-token tile of every image, recomputes the logits, forms dS with c of
+//            k_bwd_q and accumulates dk = dS^T . Q in registers.
+// The logits are recomputed from q, key and the forward's row maxima on the fp32 MFMA chain (gemm_tile<kMmaF32>,
+// the arithmetic the scorer's parity tests use); no [B,T,R] buffer exists.  The dS tile goes through LDS and both products run on
+// v_mfma_f32_32x32x2f32 too: A spans many orders of magnitude within a row, and fp32 operands keep every one of them.
+#include "gemm_kernel.h"
+
+using namespace sdg;
+
+namespace {
+
+constexpr int kT = SIXDGS_MAX_TOKENS;
+constexpr int kD = SIXDGS_D;
+constexpr float kSqrtD = 19.595917942265423f;   // (float)sqrt(384), the forward's divisor
+constexpr int kTile = 128;                       // tokens x rays of one logits tile (gemm_tile)
+constexpr int kDsLd = kTile + 1;                 // LDS row of the dS tile (odd: the transposed stores of k_bwd_q hit distinct banks)
+constexpr int kSlab = 32;                        // rows of the second operand (K or Q) staged per LDS slab
+constexpr int kOpLd = kD + 32;                   // its LDS row: the two 32-lane halves of a read land on disjoint banks
+constexpr int kOpBytes = kSlab * kOpLd * 4;
+constexpr int kGemmBytes = TileSmem<kMmaF32>::kBytes;
+constexpr int kStageBytes = kGemmBytes > kOpBytes ? kGemmBytes : kOpBytes;   // the logits' staging and the operand slab share LDS
+constexpr int kNF = kD / 2 / 32;                 // 32-feature blocks per wave column (6)
+
+struct BwdArgs {
+  const float* q;       // [B,256,384]
+  const int* n_tok;     // [B]
+  const float* key;     // [R,384]
+  const float* stats;   // [B,256,2] (max, sumexp)
+  const float* g;       // [B,R]
+  float* c;             // [B,256] workspace: c of k_bwd_q, read by k_bwd_k
+  float* ssum;          // [B,256] workspace: sum_r exp(s - max) of k_bwd_q's logits, read by k_bwd_k
+  float* dq;            // [B,256,384]
+  float* dk;            // [R,384]
+  int64_t r;
+  int batch;
+};
+
+// (max, 1 / sumexp, c) of the tile's 128 tokens into LDS; tokens at or beyond n_tok get (0, 0, 0), which makes their A exactly 0
+// (their q rows are read as zeros, so their logits are 0 and exp(0 - 0) * 0 = 0).  The max is the forward's; the sum and c are
+// k_bwd_q's (with_c), formed on the logits the backward recomputes -- so that A sums to 1 on THOSE logits: with the forward's sum
+// (other rounding of the logits) 1 - A of a ray that holds nearly all of a token's mass, and with it g - c, lost up to 9x the
+// accuracy of PyTorch's fp32 softmax backward in the peaked regime.
+__device__ __forceinline__ void load_rows(const BwdArgs& A, int b, int row0, int M, bool with_c, float* s_m, float* s_is, float* s_c) {
+  const int tid = threadIdx.x;
+  if (tid < kTile) {
+    const int t = row0 + tid;
+    const bool v = t < M;
+    const int64_t i = (int64_t)b * kT + t;
+    s_m[tid] = v ? A.stats[2 * i] : 0.f;
+    s_is[tid] = (v && with_c) ? 1.f / A.ssum[i] : 0.f;
+    s_c[tid] = (v && with_c) ? A.c[i] : 0.f;
+  }
+}
+
+// dS of this thread's 2 x 2 x 16 logits (acc: rows = tokens, columns = rays), stored to LDS as [ray][token] (TRANSPOSE, for dq) or
+// [token][ray] (for dk).  Rays at or beyond R get dS = 0 by a select (their A is not 0: the key rows read as zeros).
+template <bool TRANSPOSE>
+__device__ __forceinline__ void store_ds(const f32x16 (&acc)[2][2], const float* gv, const bool* cv, const float* s_m, const float* s_is,
+                                         const float* s_c, float* sds) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = acc_row(wm, tm, i, lane);
+      const float m = s_m[row], is = s_is[row], c = s_c[row];
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) {
+        const int col = acc_col(wn, tn, lane);
+        const float a = expf(acc[tm][tn][i] / kSqrtD - m) * is;
+        const float ds = cv[tn] ? a * (gv[tn] - c) : 0.f;
+        sds[TRANSPOSE ? col * kDsLd + row : row * kDsLd + col] = ds;
+      }
+    }
+}
+
+// out[i][f] += sum_k sds'[k][i] op[k][f] over the 128 k of the tile: sds' is the dS tile with k leading (k = ray for dq, token for dk),
+// op[k] = row k0 + k of `src` (rows >= `rows` read as zeros), staged through LDS 32 rows at a time.  Wave (wm, wn) owns rows
+// wm*64 .. +63 and features wn*192 .. +191 of the output: 2 x 6 accumulators of 32 x 32.
+__device__ __forceinline__ void ds_times_operand(const float* sds, const float* __restrict__ src, int64_t k0, int64_t rows, float* sop,
+                                                 f32x16 (&out)[2][kNF]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+  const int l31 = lane & 31, kh = lane >> 5;
+  for (int s = 0; s < kTile; s += kSlab) {
+    __syncthreads();                                  // dS stored / the previous slab consumed
+#pragma unroll
+    for (int p = 0; p < kSlab * kD / 4 / 256; ++p) {  // 12 float4 per thread
+      const int e = (p * 256 + tid) * 4, k = e / kD, f = e % kD;
+      const int64_t row = k0 + s + k;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (row < rows) v = *reinterpret_cast<const float4*>(src + row * kD + f);
+      *reinterpret_cast<float4*>(sop + k * kOpLd + f) = v;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int kk = 0; kk < kSlab; kk += 2) {
+      const int k = kk + kh;
+      const float a0 = sds[(s + k) * kDsLd + wm * 64 + l31];
+      const float a1 = sds[(s + k) * kDsLd + wm * 64 + 32 + l31];
+#pragma unroll
+      for (int j = 0; j < kNF; ++j) {
+        const float bv = sop[k * kOpLd + wn * (kD / 2) + j * 32 + l31];
+        out[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bv, out[0][j], 0, 0, 0);
+        out[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bv, out[1][j], 0, 0, 0);
+      }
+    }
+  }
+  __syncthreads();                                    // before the next logits tile restages the shared LDS
+}
+
+__device__ __forceinline__ void zero_out(f32x16 (&out)[2][kNF]) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int j = 0; j < kNF; ++j)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) out[t][j][i] = 0.f;
+}
+
+// out / sqrt(384) -> dst rows base_row + (wave rows), features of the wave; rows at or beyond `rows` are not written
+__device__ __forceinline__ void write_out(const f32x16 (&out)[2][kNF], float* __restrict__ dst, int base_row, int64_t rows) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int64_t row = (int64_t)base_row + acc_row(wm, t, i, lane);
+      if (row >= rows) continue;
+#pragma unroll
+      for (int j = 0; j < kNF; ++j) dst[row * kD + wn * (kD / 2) + j * 32 + (lane & 31)] = out[t][j][i] / kSqrtD;
+    }
+}
+
+__global__ void __launch_bounds__(256, 1) k_bwd_q(BwdArgs A) {
+  __shared__ __attribute__((aligned(16))) char stage[kStageBytes];
+  __shared__ float sds[kTile * kDsLd];
+  __shared__ float s_m[kTile], s_is[kTile], s_c[kTile], s_red[2][kTile], s_sum[2][kTile];
+  const int b = blockIdx.y, row0 = blockIdx.x * kTile;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+  const int M = min(max(A.n_tok[b], 0), kT);
+  float* dq = A.dq + ((int64_t)b * kT + row0) * kD;
+  if (row0 >= M) {                                    // no token of this tile: dq rows and c are 0
+    for (int e = tid * 4; e < kTile * kD; e += 256 * 4) *reinterpret_cast<float4*>(dq + e) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tid < kTile) {
+      A.c[(int64_t)b * kT + row0 + tid] = 0.f;
+      A.ssum[(int64_t)b * kT + row0 + tid] = 1.f;
+    }
+    return;
+  }
+  load_rows(A, b, row0, M, false, s_m, s_is, s_c);
+  __syncthreads();
+  const GemmOperands go = {A.q + (int64_t)b * kT * kD, nullptr, A.key, kD, 0, kD, M, A.r, kD, kD, nullptr, nullptr, nullptr};
+  const float* g = A.g + (int64_t)b * A.r;
+  const int n_tiles = (int)((A.r + kTile - 1) / kTile);
+  char* smem = stage;
+  // ---- sweep 1: S[t] = sum_r exp(s - max_t) and c[t] = sum_r exp(s - max_t) g[r] / S[t]; each thread sums its two columns per tile,
+  // the row owner folds lanes and waves at the end
+  float cp[2][16], sp[2][16];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) cp[t][i] = sp[t][i] = 0.f;
+  for (int tile = 0; tile < n_tiles; ++tile) {
+    const int64_t col0 = (int64_t)tile * kTile;
+    f32x16 acc[2][2];
+    gemm_tile<kMmaF32>(go, row0, col0, smem, acc);
+    float gv[2];
+    bool cv[2];
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+      const int64_t col = col0 + acc_col(wn, tn, lane);
+      cv[tn] = col < A.r;
+      gv[tn] = cv[tn] ? g[col] : 0.f;
+    }
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const float m = s_m[acc_row(wm, tm, i, lane)];
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+          const float e = cv[tn] ? expf(acc[tm][tn][i] / kSqrtD - m) : 0.f;
+          sp[tm][i] += e;
+          cp[tm][i] += e * gv[tn];
+        }
+      }
+  }
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float v = cp[tm][i], w = sp[tm][i];
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) {                            // the 32 columns of the half-wave (same row)
+        v += __shfl_xor(v, o, 64);
+        w += __shfl_xor(w, o, 64);
+      }
+      if ((lane & 31) == 0) {
+        s_red[wn][acc_row(wm, tm, i, lane)] = v;
+        s_sum[wn][acc_row(wm, tm, i, lane)] = w;
+      }
+    }
+  __syncthreads();
+  if (tid < kTile) {
+    const bool v = row0 + tid < M;
+    const float sum = v ? s_sum[0][tid] + s_sum[1][tid] : 1.f;
+    const float c = v ? (s_red[0][tid] + s_red[1][tid]) / sum : 0.f;
+    s_c[tid] = c;
+    s_is[tid] = v ? 1.f / sum : 0.f;                                 // as load_rows forms it in k_bwd_k
+    A.c[(int64_t)b * kT + row0 + tid] = c;
+    A.ssum[(int64_t)b * kT + row0 + tid] = sum;
+  }
+  __syncthreads();
+  // ---- sweep 2: dS, then dq += dS . K
+  f32x16 out[2][kNF];
+  zero_out(out);
+  float* sop = reinterpret_cast<float*>(stage);
+  for (int tile = 0; tile < n_tiles; ++tile) {
+    const int64_t col0 = (int64_t)tile * kTile;
+    f32x16 acc[2][2];
+    gemm_tile<kMmaF32>(go, row0, col0, smem, acc);
+    float gv[2];
+    bool cv[2];
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+      const int64_t col = col0 + acc_col(wn, tn, lane);
+      cv[tn] = col < A.r;
+      gv[tn] = cv[tn] ? g[col] : 0.f;
+    }
+    store_ds<true>(acc, gv, cv, s_m, s_is, s_c, sds);
+    ds_times_operand(sds, A.key, col0, A.r, sop, out);
+  }
+  write_out(out, dq, 0, kTile);                         // rows >= M hold dS = 0: zeros
+}
+
+__global__ void __launch_bounds__(256, 1) k_bwd_k(BwdArgs A) {
+  __shared__ __attribute__((aligned(16))) char stage[kStageBytes];
+  __shared__ float sds[kTile * kDsLd];
+  __shared__ float s_m[kTile], s_is[kTile], s_c[kTile];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wn = wave & 1;
+  const int64_t col0 = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * kTile;
+  float* sop = reinterpret_cast<float*>(stage);
+  f32x16 out[2][kNF];
+  zero_out(out);
+  float gv[2];
+  bool cv[2];
+  for (int b = 0; b < A.batch; ++b) {
+    const int M = min(max(A.n_tok[b], 0), kT);
+    const GemmOperands go = {A.q + (int64_t)b * kT * kD, nullptr, A.key, kD, 0, kD, M, A.r, kD, kD, nullptr, nullptr, nullptr};
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+      const int64_t col = col0 + acc_col(wn, tn, lane);
+      cv[tn] = col < A.r;
+      gv[tn] = cv[tn] ? A.g[(int64_t)b * A.r + col] : 0.f;
+    }
+    for (int row0 = 0; row0 < M; row0 += kTile) {
+      load_rows(A, b, row0, M, true, s_m, s_is, s_c);   // (the previous tile's readers passed ds_times_operand's last barrier)
+      f32x16 acc[2][2];
+      gemm_tile<kMmaF32>(go, row0, col0, stage, acc);    // its barriers publish s_m / s_is / s_c
+      store_ds<false>(acc, gv, cv, s_m, s_is, s_c, sds);
+      ds_times_operand(sds, A.q + (int64_t)b * kT * kD, row0, M, sop, out);
+    }
+  }
+  write_out(out, A.dk, (int)col0, A.r);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sixdgs_score_backward_workspace_bytes(int batch) { return 2 * sdg_align((size_t)(batch > 0 ? batch : 0) * kT * sizeof(float)); }
+
+int sixdgs_score_backward(const float* q, const int32_t* d_n_tok, int batch, const float* key, int64_t r, const float* row_stats,
+                          const float* g, float* dq, float* dk, void* ws, size_t ws_bytes, sixdgs_stream_t stream) {
+  SDG_CHECK_ARG(batch >= 0 && r >= 0);
+  if (ws_bytes < sixdgs_score_backward_workspace_bytes(batch)) return SIXDGS_E_WORKSPACE;
+  hipStream_t s = sdg_stream(stream);
+  if (r > 0 && dk == nullptr) return SIXDGS_E_BADARG;
+  if (batch == 0 || r == 0) {                         // nothing to contract: zero gradients
+    if (batch > 0) {
+      SDG_CHECK_ARG(dq != nullptr);
+      hipError_t e = hipMemsetAsync(dq, 0, (size_t)batch * kT * kD * sizeof(float), s);
+      if (e != hipSuccess) return (int)e;
+    }
+    if (r > 0) {
+      hipError_t e = hipMemsetAsync(dk, 0, (size_t)r * kD * sizeof(float), s);
+      if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+  }
+  SDG_CHECK_ARG(q && d_n_tok && key && row_stats && g && dq && ws);
+  SDG_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)key % 16) == 0 && ((uintptr_t)dq % 16) == 0 && ((uintptr_t)dk % 16) == 0);
+  SDG_CHECK_ARG(batch <= 65535 && r <= (int64_t)kTile * 0x7fffffff);
+  float* c = (float*)ws;
+  float* ssum = (float*)((char*)ws + sdg_align((size_t)batch * kT * sizeof(float)));
+  BwdArgs A = {q, d_n_tok, key, row_stats, g, c, ssum, dq, dk, r, batch};
+  hipLaunchKernelGGL(k_bwd_q, dim3(kT / kTile, (unsigned)batch), dim3(256), 0, s, A);
+  SDG_LAUNCH_OK();
+  hipLaunchKernelGGL(k_bwd_k, dim3((unsigned)sdg_cdiv(r, kTile)), dim3(256), 0, s, A);
+  SDG_LAUNCH_OK();
+  return 0;
+}
+
+}  // extern "C"

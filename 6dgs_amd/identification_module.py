@@ -558,3 +558,40 @@ class IdentificationModule(torch.nn.Module):
         scores = attention_map.sum(dim=0)
         up = torch.nn.functional.normalize(self.camera_direction_prediction_network(fmap), dim=-1)
         return scores, attention_map, t_flat, up, used
+
+    def forward_window(self, imgs, masks, rays_ori: torch.Tensor, rays_dir: torch.Tensor, rays_rgb: torch.Tensor):
+        """The training forward of a whole window of images at once (train_id_module(batched_window=True)).  Every image of the window
+        is scored against the SAME keys K = k_proj(ray MLP(rays)), so the ray side runs once -- on the rays as given, unpermuted: the
+        scores are permutation-equivariant and the loss is a mean over the rays -- and its backward receives the gradient of all images
+        at once.  The image side is frozen (one batch through image_tokens, no autograd); q_proj, the scorer (ops.ray_attention_scores:
+        the two-pass scorer forward, sixdgs_score_backward) and the camera-up CNN carry gradients.  On the CPU or with hip_autograd False
+        the scorer is PyTorch's softmax and column sum per image.  imgs / masks as image_tokens takes them (mask None = every pixel; a mask
+        selects the image's tokens by boolean indexing, the one host sync of a window with masked images).
+        Returns (scores [B,R], camera-up [B,3] (unit), token counts [B] as a host list)."""
+        toks, fmaps = self.image_tokens(imgs, masks)
+        if isinstance(toks, BatchedTokens):
+            toks = toks.dense()
+        device = rays_ori.device
+        if torch.is_tensor(toks):                       # every image keeps all its tokens
+            b, n_host = toks.shape[0], [int(toks.shape[1])] * toks.shape[0]
+            tokens = toks
+        else:
+            b, n_host = len(toks), [int(t.shape[0]) for t in toks]
+            tokens = toks[0].new_zeros(b, ops.MAX_TOKENS, toks[0].shape[-1])
+            for i, t in enumerate(toks):
+                tokens[i, : t.shape[0]] = t
+        feat = self.ray_features_autograd(rays_ori, rays_dir, rays_rgb)
+        at = self.attention
+        if feat.is_cuda and self.hip_autograd:
+            from . import autograd as hip
+            n_tok = self._full_ntok(b, device) if all(n == ops.MAX_TOKENS for n in n_host) else \
+                torch.stack([torch.full((), n, dtype=torch.int32, device=device) for n in n_host])      # device-side: no host copy
+            q = hip.linear(tokens.reshape(b * ops.MAX_TOKENS, -1), at.q_proj.weight, at.q_proj.bias).view(b, ops.MAX_TOKENS, -1)
+            k = hip.linear(feat, at.k_proj.weight, at.k_proj.bias)
+            scores = ops.ray_attention_scores(q, n_tok, k)
+        else:
+            q, k = at.q_proj(tokens), at.k_proj(feat)
+            scale = q.shape[-1] ** 0.5
+            scores = torch.stack([torch.softmax((q[i, :n] @ k.transpose(-2, -1)) / scale, dim=-1).sum(dim=0) for i, n in enumerate(n_host)])
+        up = torch.nn.functional.normalize(self.camera_direction_prediction_network(fmaps), dim=-1)
+        return scores, up, n_host

@@ -1001,6 +1001,77 @@ def score_pass2(stats: torch.Tensor, n_tok: torch.Tensor, r: int, workspace: tor
     return idx, val, scores
 
 
+def _check_scorer_operands(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor):
+    """The operand contract of ray_attention_scores / score_backward: fp32 q [B,256,384] and key [R,384], int32 n_tok [B], contiguous, on one GPU."""
+    _need_gpu(q, n_tok, k)
+    if q.dtype != torch.float32 or k.dtype != torch.float32:
+        raise RuntimeError(f"6dgs_amd: q and k must be float32 (got {q.dtype}, {k.dtype})")
+    if q.dim() != 3 or tuple(q.shape[1:]) != (MAX_TOKENS, D):
+        raise RuntimeError(f"6dgs_amd: q must be [B,{MAX_TOKENS},{D}] (got {tuple(q.shape)})")
+    if k.dim() != 2 or k.shape[1] != D or k.shape[0] < 1:
+        raise RuntimeError(f"6dgs_amd: k must be [R,{D}] with R >= 1 (got {tuple(k.shape)})")
+    if n_tok.dtype != torch.int32 or tuple(n_tok.shape) != (q.shape[0],):
+        raise RuntimeError(f"6dgs_amd: n_tok must be int32 [{q.shape[0]}] (got {n_tok.dtype} {tuple(n_tok.shape)})")
+    if not (q.is_contiguous() and k.is_contiguous() and n_tok.is_contiguous()):
+        raise RuntimeError("6dgs_amd: q, n_tok and k must be contiguous")
+
+
+@_on_device
+def score_backward(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor, row_stats: torch.Tensor, g: torch.Tensor):
+    """include/sixdgs.h: sixdgs_score_backward.  (dq [B,256,384], dk [R,384]) of scores[b][r] = sum_t softmax_r(q[b][t] . k[r] / sqrt(384))
+    for the upstream gradient g [B,R], from the forward's row statistics [B,256,2]; dq rows at or beyond n_tok[b] are zeros."""
+    _check_scorer_operands(q, n_tok, k)
+    b, r = q.shape[0], k.shape[0]
+    if tuple(row_stats.shape) != (b, MAX_TOKENS, 2) or tuple(g.shape) != (b, r):
+        raise RuntimeError(f"6dgs_amd: row_stats must be [{b},{MAX_TOKENS},2] and g [{b},{r}] (got {tuple(row_stats.shape)}, {tuple(g.shape)})")
+    row_stats, g = _f32(row_stats), _f32(g)
+    _need_gpu(row_stats, g)
+    lib = _lib.load()
+    dq = torch.empty_like(q)
+    dk = torch.empty_like(k)
+    ws = torch.empty(max(1, lib.sixdgs_score_backward_workspace_bytes(b)), dtype=torch.uint8, device=q.device)
+    check(lib.sixdgs_score_backward(_p(q), _p(n_tok), b, _p(k), r, _p(row_stats), _p(g), _p(dq), _p(dk), _p(ws), ws.numel(), _stream()),
+          "score_backward")
+    return dq, dk
+
+
+@_on_device
+def _ray_attention_forward(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor):
+    """(scores [B,R], row statistics [B,256,2]) of the two-pass scorer, on the key's scaled fp16 planes in the F16X3 modes."""
+    _check_scorer_operands(q, n_tok, k)
+    b, r = q.shape[0], k.shape[0]
+    planes = effective_mma_mode() in F16_MODES
+    kp, ks = split_planes_f16(k) if planes else (None, None)
+    ws = torch.empty(score_topk_workspace_bytes(r, b, 1, planes=planes), dtype=torch.uint8, device=q.device)
+    stats = score_pass1(q, n_tok, k, ws, 1, key_planes=kp, key_scale=ks)
+    _, _, scores = score_pass2(stats, n_tok, r, ws, 1, used_planes=planes)
+    return scores, stats
+
+
+class RayAttentionScores(torch.autograd.Function):
+    """scores [B,R] = sum_t softmax_r(q[b][t] . k[r] / sqrt(384)) over the first n_tok[b] tokens.  Forward: the two-pass scorer
+    (score_pass1 on the key's scaled fp16 planes, score_pass2); backward: sixdgs_score_backward from the saved row statistics."""
+
+    @staticmethod
+    def forward(ctx, q, n_tok, k):
+        q, k = q.detach(), k.detach()
+        scores, stats = _ray_attention_forward(q, n_tok, k)
+        ctx.save_for_backward(q, n_tok, k, stats)
+        return scores
+
+    @staticmethod
+    def backward(ctx, g):
+        q, n_tok, k, stats = ctx.saved_tensors
+        dq, dk = score_backward(q, n_tok, k, stats, g.contiguous())
+        return dq if ctx.needs_input_grad[0] else None, None, dk if ctx.needs_input_grad[2] else None
+
+
+def ray_attention_scores(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
+    """Differentiable scorer of training: q fp32 [B,256,384] (rows at or beyond n_tok[b] are ignored), n_tok int32 [B] on the device,
+    k fp32 [R,384] -> scores [B,R]; gradients reach q and k (RayAttentionScores)."""
+    return RayAttentionScores.apply(q, n_tok, k)
+
+
 @_on_device
 def topk(scores: torch.Tensor, k: int = 100):
     scores = _f32(scores)

@@ -52,6 +52,8 @@ def parse_args(argv=None):
     ap.add_argument("--max_ellipsoids", type=int, default=1000, help="ellipsoids that emit rays (1000 = the reference; -1 = every valid Gaussian)")
     ap.add_argument("--rays_per_ellipsoid", type=int, default=64, help="iso-cell emitter only")
     ap.add_argument("--n_iterations", type=int, default=1500, help="training iterations when no id_module.th exists")
+    ap.add_argument("--batched_window", action="store_true",
+                    help="train each iteration's 32 images as one window (one ray-MLP pass; train_id_module(batched_window=True)) instead of one by one")
     ap.add_argument("--skip_train", action="store_true", help="never train: evaluate the checkpoint, or random-init weights when there is none")
     ap.add_argument("--batch_size", type=int, default=16, help="query images per scorer launch")
     ap.add_argument("--arena_gb", type=float, default=0.0,
@@ -75,7 +77,8 @@ def explore_model(model, **emission):
 
 def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[str, Any]", exp_dir_filepath: str, object_id: str, category_name: str,
                            starting_seed: int, lock_backbone: bool = True, device: str = "cuda", *, emission: Optional[dict] = None,
-                           n_iterations: int = 1500, skip_train: bool = False, batch_size: int = 16, backbone: Optional[torch.nn.Module] = None):
+                           n_iterations: int = 1500, skip_train: bool = False, batch_size: int = 16, backbone: Optional[torch.nn.Module] = None,
+                           batched_window: bool = False):
     """pretrain_eval_attention.py:31-160 for one scene; returns the result dicts of the inference pass for ALL test views (rank 0;
     other ranks return their own block).
 
@@ -110,7 +113,8 @@ def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[s
     def stage_train():
         if not skip_train and start_iterations < n_iterations and dd.rank() == 0:
             train_id_module(ckpt_path, device, id_module, partial(explore_model, gs_model, **emission), scene_info, object_id, category_name,
-                            start_iterations=start_iterations, lock_backbone=lock_backbone, n_iterations=n_iterations)
+                            start_iterations=start_iterations, lock_backbone=lock_backbone, n_iterations=n_iterations,
+                            batched_window=batched_window)
 
     dd.agree(stage_train, "train the scorer (rank 0)", device, long_wait=True)
     dd.broadcast_module(id_module, 0)
@@ -192,7 +196,8 @@ def main(argv=None, backbone: Optional[torch.nn.Module] = None) -> List[dict]:
                 exp["checkpoint_filepath"], ckpt_args, exp["exp_dir_filepath"], exp["sequence_id"], exp["category_name"], starting_seed=55176280,
                 device=device, lock_backbone=True,
                 emission=dict(emitter=args.emitter, max_ellipsoids=args.max_ellipsoids, rays_per_ellipsoid=args.rays_per_ellipsoid),
-                n_iterations=args.n_iterations, skip_train=args.skip_train, batch_size=args.batch_size, backbone=backbone)
+                n_iterations=args.n_iterations, skip_train=args.skip_train, batch_size=args.batch_size, backbone=backbone,
+                batched_window=args.batched_window)
             if rank == 0:
                 results.extend(obj)
         except RuntimeError:            # the only exception the reference survives per scene (pretrain_eval_attention.py:243-244)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SIXDGS_ABI_VERSION 7   /* 7: sixdgs_image_prep (uint8 -> resized, cropped, normalised planar fp32 in one pass); 6: sixdgs_tok_pack / sixdgs_tok_linear (dense products of the backbone stage on packed weight planes, with LayerNorm / GELU / residual fusion), sixdgs_tok_attention, sixdgs_im2col, sixdgs_u8_to_planar; the three-plane bf16 key format and its scorer kernel removed (sixdgs_split_planes, sixdgs_key_planes_bytes gone; key planes exist as scaled fp16 only); 5: sixdgs_scorer_weights carries the composite layer w4k / b4k / m4k (k_proj folded into ray-MLP layer 4 on the key-cache path), sixdgs_select_begin / _sample_stats take h_n_tok (token packing of the select sweep); 4: the select path's slack derived from |q| |k| (sixdgs_key_planes_norm_max; q + d_key_norm_max arguments) and its ray-sharded form (sample_stats / prepare / topk_u, d_uk, allow_fewer), tile maxima of U (u_tile_max); 3: sixdgs_score_select + sixdgs_select_* stages (top-k without materialised logits); 2: plane-format scorer entry points, pass1/pass2, grid kNN, split-K, distance target */
+#define SIXDGS_ABI_VERSION 8   /* 8: sixdgs_score_backward / sixdgs_score_backward_workspace_bytes (backward of the scorer for training); 7: sixdgs_image_prep (uint8 -> resized, cropped, normalised planar fp32 in one pass); 6: sixdgs_tok_pack / sixdgs_tok_linear (dense products of the backbone stage on packed weight planes, with LayerNorm / GELU / residual fusion), sixdgs_tok_attention, sixdgs_im2col, sixdgs_u8_to_planar; the three-plane bf16 key format and its scorer kernel removed (sixdgs_split_planes, sixdgs_key_planes_bytes gone; key planes exist as scaled fp16 only); 5: sixdgs_scorer_weights carries the composite layer w4k / b4k / m4k (k_proj folded into ray-MLP layer 4 on the key-cache path), sixdgs_select_begin / _sample_stats take h_n_tok (token packing of the select sweep); 4: the select path's slack derived from |q| |k| (sixdgs_key_planes_norm_max; q + d_key_norm_max arguments) and its ray-sharded form (sample_stats / prepare / topk_u, d_uk, allow_fewer), tile maxima of U (u_tile_max); 3: sixdgs_score_select + sixdgs_select_* stages (top-k without materialised logits); 2: plane-format scorer entry points, pass1/pass2, grid kNN, split-K, distance target */
 #define SIXDGS_E_BADARG (-1)
 #define SIXDGS_E_WORKSPACE (-2)
 #define SIXDGS_E_UNSUPPORTED (-3)
@@ -321,6 +321,17 @@ int sixdgs_score_pass1(const float* q, const int32_t* d_n_tok, const int32_t* h_
                        size_t ws_bytes, sixdgs_stream_t stream, sixdgs_profile* prof, int mma_mode);
 int sixdgs_score_pass2(const float* row_stats, const int32_t* d_n_tok, int batch, int used_planes, int64_t r, int topk,
                        float* scores, int64_t* idx, float* val, void* ws, size_t ws_bytes, sixdgs_stream_t stream, int mma_mode);
+/* Backward of scores[b][r] = sum_t softmax_r(q[b][t] . key[r] / sqrt(384)) (training).  g [B,R] = dL/dscores; row_stats [B,256,2] =
+ * the forward's (max, sumexp), as sixdgs_score_pass1 returns them.  With A = softmax, c[b][t] = sum_r A g and dS = A (g - c):
+ *   dq [B,256,384] = sum_r dS key[r] / sqrt(384)          rows t >= d_n_tok[b] are written as zeros (and q's rows there are not read)
+ *   dk [R,384]     = sum_b sum_t dS q[b][t] / sqrt(384)
+ * The logits are recomputed from q and key (fp32 MFMA) with the forward's max as the exponent offset; the softmax sum is recomputed
+ * with c, on the same logits.  Nothing of size B x T x R is stored.  No floating-point atomics: the same inputs give the same bits.
+ * d_n_tok[b] = 0 is legal and contributes nothing.  ws: sixdgs_score_backward_workspace_bytes(batch) bytes (c and the sums, 2 x B x 256
+ * floats).  q, key, dq and dk 16-byte aligned, all arrays dense. */
+size_t sixdgs_score_backward_workspace_bytes(int batch);
+int sixdgs_score_backward(const float* q, const int32_t* d_n_tok, int batch, const float* key /*[R,384]*/, int64_t r,
+                          const float* row_stats, const float* g, float* dq, float* dk, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
 /* Top-k WITHOUT materialising the logits -- the inference path, where only idx/val are wanted (the reference driver reads nothing
  * else: test.py:105-107).  Needs the scaled fp16 key planes of ALL r rays (sixdgs_ray_keys_ex, SIXDGS_MMA_F16X3) and those of a
  * ray SAMPLE (any r_sample <= r rays of the same scene, e.g. one ray in 16, through the same entry point).  score[r] =
