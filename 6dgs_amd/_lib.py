@@ -22,7 +22,7 @@ sz = C.c_size_t
 
 
 PROFILE_SLOTS = 128
-ABI_VERSION = 8          # must equal SIXDGS_ABI_VERSION in include/sixdgs.h (checked by __graft_entry__.post_build_checks)
+ABI_VERSION = 9          # must equal SIXDGS_ABI_VERSION in include/sixdgs.h (checked by __graft_entry__.post_build_checks)
 
 
 class Profile(C.Structure):
@@ -63,6 +63,8 @@ SIGNATURES = {
     "sixdgs_score_pass2": (i32, [vp, vp, i32, i32, i64, i32, vp, vp, vp, vp, sz, vp, i32]),
     "sixdgs_score_backward_workspace_bytes": (sz, [i32]),
     "sixdgs_score_backward": (i32, [vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, sz, vp]),
+    "sixdgs_score_backward_split_workspace_bytes": (sz, [i32, i64, i32]),
+    "sixdgs_score_backward_split": (i32, [vp, vp, i32, vp, i64, vp, vp, vp, vp, i32, vp, sz, vp]),
     "sixdgs_score_topk_ex": (i32, [vp, vp, vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Profile), i32]),
     "sixdgs_score_select_workspace_bytes": (sz, [i64, i32, i32, i32]),
     "sixdgs_score_select": (i32, [vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, sz, vp, C.POINTER(Profile)]),

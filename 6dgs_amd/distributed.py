@@ -263,6 +263,75 @@ def agree(fn: Callable, what: str = "", device=None, long_wait: bool = False):
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# data-parallel training (train_id_module(data_parallel=True))
+# ---------------------------------------------------------------------------------------------
+def sum_gradients(params, logs: torch.Tensor, failed: bool = False, group=None) -> torch.Tensor:
+    """The one collective of a data-parallel training iteration: the gradients of `params` (the optimiser's parameters, in its order),
+    the logged sums `logs` [n] and a failure flag go into ONE fp32 bucket, which is all-reduced (SUM) on `group` (default: the long-wait
+    group -- rank 0 evaluates and checkpoints between two iterations while the others wait here); the summed gradients are written back
+    into p.grad.  Returns the summed logs, identical on every rank.
+
+    failed: this rank's window step raised; it contributes zero gradients and zero logs.  A parameter without a gradient (on a rank that
+    did not fail) is an error, not a silent zero: it raises the flag too.  When any rank raised the flag, EVERY rank raises RuntimeError
+    after the reduce -- the ranks leave the scene together (as agree() makes them do) instead of one waiting in the next collective.
+    Without a process group: the gradients stay as they are, and a flag or a missing gradient raises at once."""
+    params = list(params)
+    missing = [i for i, p in enumerate(params) if p.grad is None]
+    logs = logs.detach().reshape(-1)
+    dev = logs.device
+    bad = bool(failed) or bool(missing)
+    if not is_dist():
+        if failed:
+            raise RuntimeError("6dgs_amd: the window step failed")
+        if missing:
+            raise RuntimeError(f"6dgs_amd: sum_gradients: parameters {missing} of the optimiser have no gradient")
+        return logs
+    parts = [torch.zeros(p.numel(), dtype=torch.float32, device=dev) if bad else p.grad.detach().reshape(-1).to(device=dev, dtype=torch.float32)
+             for p in params]
+    parts.append(torch.zeros_like(logs, dtype=torch.float32) if bad else logs.to(torch.float32))
+    parts.append(torch.full((1,), 1.0 if bad else 0.0, dtype=torch.float32, device=dev))
+    bucket = _collective_device(torch.cat(parts))
+    dist.all_reduce(bucket, op=dist.ReduceOp.SUM, group=long_wait_group() if group is None else group)
+    if float(bucket[-1]) > 0:
+        if missing and not failed:
+            raise RuntimeError(f"6dgs_amd: sum_gradients: parameters {missing} of the optimiser have no gradient on rank {dist.get_rank()}")
+        raise RuntimeError(f"6dgs_amd: a training window step failed on {int(float(bucket[-1]))} rank(s); rank {dist.get_rank()} leaves the scene with it")
+    off = 0
+    for p in params:
+        n = p.numel()
+        p.grad.copy_(bucket[off: off + n].view_as(p.grad))
+        off += n
+    return bucket[off: off + logs.numel()].to(dev)
+
+
+def broadcast_tensor(t: Optional[torch.Tensor], src: int, device, dtype=torch.float32, shape=None, group=None) -> torch.Tensor:
+    """A tensor of rank `src` (1-D or 2-D; `t` is ignored elsewhere) on every rank, on `device`.  shape None: the shape is broadcast first,
+    so the other ranks need not know it; otherwise every rank passes the same `shape`.  Default group: the long-wait one (data-parallel
+    training: rank 0 may be evaluating while the others wait here)."""
+    if not is_dist():
+        return t
+    g = long_wait_group() if group is None else group
+    host = dist.get_backend() == "gloo"
+    if shape is None:
+        meta = torch.zeros(3, dtype=torch.int64, device="cpu" if host else device)
+        if dist.get_rank() == src:
+            shp = list(t.shape)
+            if len(shp) not in (1, 2):
+                raise RuntimeError(f"6dgs_amd: broadcast_tensor takes 1-D or 2-D tensors (got {tuple(t.shape)})")
+            meta = torch.tensor([len(shp)] + shp + [0] * (2 - len(shp)), dtype=torch.int64, device=meta.device)
+        dist.broadcast(meta, src, group=g)
+        nd, shp = int(meta[0]), [int(x) for x in meta[1:]]
+        shape = shp[:nd]
+    if dist.get_rank() == src:
+        buf = t.detach().to(dtype).contiguous()
+        buf = buf.cpu() if host else buf.to(device)
+    else:
+        buf = torch.empty(shape, dtype=dtype, device="cpu" if host else device)
+    dist.broadcast(buf, src, group=g)
+    return buf.to(device)
+
+
 def backend_name() -> str:
     """"nccl" (= RCCL on ROCm) / "gloo" when a process group is up, "none" for a single process."""
     return dist.get_backend() if is_dist() else "none"

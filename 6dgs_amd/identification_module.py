@@ -559,14 +559,15 @@ class IdentificationModule(torch.nn.Module):
         up = torch.nn.functional.normalize(self.camera_direction_prediction_network(fmap), dim=-1)
         return scores, attention_map, t_flat, up, used
 
-    def forward_window(self, imgs, masks, rays_ori: torch.Tensor, rays_dir: torch.Tensor, rays_rgb: torch.Tensor):
+    def forward_window(self, imgs, masks, rays_ori: torch.Tensor, rays_dir: torch.Tensor, rays_rgb: torch.Tensor, ray_groups: int = 1):
         """The training forward of a whole window of images at once (train_id_module(batched_window=True)).  Every image of the window
         is scored against the SAME keys K = k_proj(ray MLP(rays)), so the ray side runs once -- on the rays as given, unpermuted: the
         scores are permutation-equivariant and the loss is a mean over the rays -- and its backward receives the gradient of all images
         at once.  The image side is frozen (one batch through image_tokens, no autograd); q_proj, the scorer (ops.ray_attention_scores:
         the two-pass scorer forward, sixdgs_score_backward) and the camera-up CNN carry gradients.  On the CPU or with hip_autograd False
         the scorer is PyTorch's softmax and column sum per image.  imgs / masks as image_tokens takes them (mask None = every pixel; a mask
-        selects the image's tokens by boolean indexing, the one host sync of a window with masked images).
+        selects the image's tokens by boolean indexing, the one host sync of a window with masked images).  ray_groups: the split of the
+        scorer's backward over the rays (ops.ray_attention_scores; 1 = unsplit, 0 = auto; ignored by the PyTorch scorer).
         Returns (scores [B,R], camera-up [B,3] (unit), token counts [B] as a host list)."""
         toks, fmaps = self.image_tokens(imgs, masks)
         if isinstance(toks, BatchedTokens):
@@ -588,7 +589,7 @@ class IdentificationModule(torch.nn.Module):
                 torch.stack([torch.full((), n, dtype=torch.int32, device=device) for n in n_host])      # device-side: no host copy
             q = hip.linear(tokens.reshape(b * ops.MAX_TOKENS, -1), at.q_proj.weight, at.q_proj.bias).view(b, ops.MAX_TOKENS, -1)
             k = hip.linear(feat, at.k_proj.weight, at.k_proj.bias)
-            scores = ops.ray_attention_scores(q, n_tok, k)
+            scores = ops.ray_attention_scores(q, n_tok, k, ray_groups)
         else:
             q, k = at.q_proj(tokens), at.k_proj(feat)
             scale = q.shape[-1] ** 0.5

@@ -1017,9 +1017,14 @@ def _check_scorer_operands(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor
 
 
 @_on_device
-def score_backward(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor, row_stats: torch.Tensor, g: torch.Tensor):
+def score_backward(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor, row_stats: torch.Tensor, g: torch.Tensor, ray_groups: int = 1):
     """include/sixdgs.h: sixdgs_score_backward.  (dq [B,256,384], dk [R,384]) of scores[b][r] = sum_t softmax_r(q[b][t] . k[r] / sqrt(384))
-    for the upstream gradient g [B,R], from the forward's row statistics [B,256,2]; dq rows at or beyond n_tok[b] are zeros."""
+    for the upstream gradient g [B,R], from the forward's row statistics [B,256,2]; dq rows at or beyond n_tok[b] are zeros.
+    ray_groups: 1 (default) = sixdgs_score_backward; G > 1 splits each token tile's rays into G groups (sixdgs_score_backward_split: 2 x B x G
+    workgroups instead of 2 x B, partial sums reduced in a fixed order, other rounding than G = 1); 0 = G chosen from the CU count, B and R."""
+    ray_groups = int(ray_groups)
+    if ray_groups < 0:
+        raise ValueError(f"6dgs_amd: ray_groups must be >= 0 (got {ray_groups})")
     _check_scorer_operands(q, n_tok, k)
     b, r = q.shape[0], k.shape[0]
     if tuple(row_stats.shape) != (b, MAX_TOKENS, 2) or tuple(g.shape) != (b, r):
@@ -1029,9 +1034,14 @@ def score_backward(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor, row_st
     lib = _lib.load()
     dq = torch.empty_like(q)
     dk = torch.empty_like(k)
-    ws = torch.empty(max(1, lib.sixdgs_score_backward_workspace_bytes(b)), dtype=torch.uint8, device=q.device)
-    check(lib.sixdgs_score_backward(_p(q), _p(n_tok), b, _p(k), r, _p(row_stats), _p(g), _p(dq), _p(dk), _p(ws), ws.numel(), _stream()),
-          "score_backward")
+    if ray_groups == 1:
+        ws = torch.empty(max(1, lib.sixdgs_score_backward_workspace_bytes(b)), dtype=torch.uint8, device=q.device)
+        check(lib.sixdgs_score_backward(_p(q), _p(n_tok), b, _p(k), r, _p(row_stats), _p(g), _p(dq), _p(dk), _p(ws), ws.numel(), _stream()),
+              "score_backward")
+    else:
+        ws = torch.empty(max(1, lib.sixdgs_score_backward_split_workspace_bytes(b, r, ray_groups)), dtype=torch.uint8, device=q.device)
+        check(lib.sixdgs_score_backward_split(_p(q), _p(n_tok), b, _p(k), r, _p(row_stats), _p(g), _p(dq), _p(dk), ray_groups, _p(ws), ws.numel(),
+                                              _stream()), "score_backward_split")
     return dq, dk
 
 
@@ -1050,26 +1060,31 @@ def _ray_attention_forward(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor
 
 class RayAttentionScores(torch.autograd.Function):
     """scores [B,R] = sum_t softmax_r(q[b][t] . k[r] / sqrt(384)) over the first n_tok[b] tokens.  Forward: the two-pass scorer
-    (score_pass1 on the key's scaled fp16 planes, score_pass2); backward: sixdgs_score_backward from the saved row statistics."""
+    (score_pass1 on the key's scaled fp16 planes, score_pass2); backward: sixdgs_score_backward from the saved row statistics (split over
+    ray_groups groups of rays when ray_groups != 1: score_backward)."""
 
     @staticmethod
-    def forward(ctx, q, n_tok, k):
+    def forward(ctx, q, n_tok, k, ray_groups=1):
         q, k = q.detach(), k.detach()
         scores, stats = _ray_attention_forward(q, n_tok, k)
         ctx.save_for_backward(q, n_tok, k, stats)
+        ctx.ray_groups = ray_groups
         return scores
 
     @staticmethod
     def backward(ctx, g):
         q, n_tok, k, stats = ctx.saved_tensors
-        dq, dk = score_backward(q, n_tok, k, stats, g.contiguous())
-        return dq if ctx.needs_input_grad[0] else None, None, dk if ctx.needs_input_grad[2] else None
+        dq, dk = score_backward(q, n_tok, k, stats, g.contiguous(), ray_groups=ctx.ray_groups)
+        return dq if ctx.needs_input_grad[0] else None, None, dk if ctx.needs_input_grad[2] else None, None
 
 
-def ray_attention_scores(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
+def ray_attention_scores(q: torch.Tensor, n_tok: torch.Tensor, k: torch.Tensor, ray_groups: int = 1) -> torch.Tensor:
     """Differentiable scorer of training: q fp32 [B,256,384] (rows at or beyond n_tok[b] are ignored), n_tok int32 [B] on the device,
-    k fp32 [R,384] -> scores [B,R]; gradients reach q and k (RayAttentionScores)."""
-    return RayAttentionScores.apply(q, n_tok, k)
+    k fp32 [R,384] -> scores [B,R]; gradients reach q and k (RayAttentionScores).  ray_groups: the backward's split over the rays
+    (score_backward; 1 = the unsplit kernels, 0 = auto)."""
+    if int(ray_groups) < 0:
+        raise ValueError(f"6dgs_amd: ray_groups must be >= 0 (got {ray_groups})")
+    return RayAttentionScores.apply(q, n_tok, k, int(ray_groups))
 
 
 @_on_device

@@ -54,13 +54,23 @@ def parse_args(argv=None):
     ap.add_argument("--n_iterations", type=int, default=1500, help="training iterations when no id_module.th exists")
     ap.add_argument("--batched_window", action="store_true",
                     help="train each iteration's 32 images as one window (one ray-MLP pass; train_id_module(batched_window=True)) instead of one by one")
+    ap.add_argument("--data_parallel_train", action="store_true",
+                    help="with --batched_window: every rank trains its block of each window, gradients summed by one all-reduce per iteration "
+                         "(train_id_module(data_parallel=True)) instead of rank 0 training alone")
+    ap.add_argument("--backward_ray_groups", type=int, default=1,
+                    help="split of the scorer's backward over the rays in the window (1 = unsplit, 0 = auto from the CU count)")
     ap.add_argument("--skip_train", action="store_true", help="never train: evaluate the checkpoint, or random-init weights when there is none")
     ap.add_argument("--batch_size", type=int, default=16, help="query images per scorer launch")
     ap.add_argument("--arena_gb", type=float, default=0.0,
                     help="carve the big per-scene buffers (key planes, select workspace, chain workspace) from ONE device buffer of this many GB allocated once "
                          "(ops.Arena) instead of asking the allocator scene by scene: a sweep over scenes of growing size otherwise pays a 100-200 GB hipMalloc "
                          "per scene.  -1: everything free but 56 GB; 0 (default): off")
-    return ap.parse_known_args(argv)
+    args, rest = ap.parse_known_args(argv)
+    if args.data_parallel_train and not args.batched_window:
+        ap.error("--data_parallel_train needs --batched_window")
+    if args.backward_ray_groups < 0:
+        ap.error("--backward_ray_groups must be >= 0 (0 = auto)")
+    return args, rest
 
 
 def load_model(checkpoint_path, device, sh_degrees=3):
@@ -78,7 +88,7 @@ def explore_model(model, **emission):
 def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[str, Any]", exp_dir_filepath: str, object_id: str, category_name: str,
                            starting_seed: int, lock_backbone: bool = True, device: str = "cuda", *, emission: Optional[dict] = None,
                            n_iterations: int = 1500, skip_train: bool = False, batch_size: int = 16, backbone: Optional[torch.nn.Module] = None,
-                           batched_window: bool = False):
+                           batched_window: bool = False, data_parallel_train: bool = False, backward_ray_groups: int = 1):
     """pretrain_eval_attention.py:31-160 for one scene; returns the result dicts of the inference pass for ALL test views (rank 0;
     other ranks return their own block).
 
@@ -86,7 +96,8 @@ def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[s
     failure flag behind it and leave the scene TOGETHER on a RuntimeError of any of them); the collectives (scene / weight
     broadcast, seed, result gather) sit between the stages, where every rank is known to arrive.  Rank 0 trains a missing
     checkpoint inside a stage while the others wait in that stage's all-reduce (on the group with the long timeout: agree(long_wait=True),
-    distributed.init_from_env)."""
+    distributed.init_from_env).  data_parallel_train: every rank takes part in the training (train_id_module(data_parallel=True)), inside
+    the same stage; the ranks of a failing iteration leave it together."""
     torch.manual_seed(starting_seed)
     print("data_path: ", checkpoint_args.source_path)
     emission = dict(EMISSION, **(emission or {}))
@@ -111,12 +122,12 @@ def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[s
     gs_model = dd.broadcast_scene(scene, 0, device=device)
 
     def stage_train():
-        if not skip_train and start_iterations < n_iterations and dd.rank() == 0:
+        if not skip_train and start_iterations < n_iterations and (dd.rank() == 0 or data_parallel_train):
             train_id_module(ckpt_path, device, id_module, partial(explore_model, gs_model, **emission), scene_info, object_id, category_name,
                             start_iterations=start_iterations, lock_backbone=lock_backbone, n_iterations=n_iterations,
-                            batched_window=batched_window)
+                            batched_window=batched_window, data_parallel=data_parallel_train, backward_ray_groups=backward_ray_groups)
 
-    dd.agree(stage_train, "train the scorer (rank 0)", device, long_wait=True)
+    dd.agree(stage_train, "train the scorer (every rank)" if data_parallel_train else "train the scorer (rank 0)", device, long_wait=True)
     dd.broadcast_module(id_module, 0)
     id_module.eval()
     id_module.invalidate_caches()
@@ -197,7 +208,8 @@ def main(argv=None, backbone: Optional[torch.nn.Module] = None) -> List[dict]:
                 device=device, lock_backbone=True,
                 emission=dict(emitter=args.emitter, max_ellipsoids=args.max_ellipsoids, rays_per_ellipsoid=args.rays_per_ellipsoid),
                 n_iterations=args.n_iterations, skip_train=args.skip_train, batch_size=args.batch_size, backbone=backbone,
-                batched_window=args.batched_window)
+                batched_window=args.batched_window, data_parallel_train=args.data_parallel_train,
+                backward_ray_groups=args.backward_ray_groups)
             if rank == 0:
                 results.extend(obj)
         except RuntimeError:            # the only exception the reference survives per scene (pretrain_eval_attention.py:243-244)

@@ -74,14 +74,16 @@ class _GateGrad(torch.autograd.Function):
         return torch.where(keep.view(-1, *([1] * (g.dim() - 1))), g, torch.zeros_like(g)), None
 
 
-def window_step_loss(id_module, imgs, masks, poses, rays_ori, rays_dirs, rays_rgb, model_up, gradient_accumulation_steps: int):
+def window_step_loss(id_module, imgs, masks, poses, rays_ori, rays_dirs, rays_rgb, model_up, gradient_accumulation_steps: int, ray_groups: int = 1):
     """The accumulated steps of one iteration as ONE window (train_id_module(batched_window=True)): forward_window on all images, the
     targets of ops.distance_target, per image score loss + 0.1 x camera-up loss, and their sum over the images whose combined loss is
-    finite, divided by gradient_accumulation_steps -- the value whose gradient the per-image loop accumulates.  An image whose combined
+    finite, divided by gradient_accumulation_steps -- the value whose gradient the per-image loop accumulates (a data-parallel rank passes
+    its block of the draws and the GLOBAL gradient_accumulation_steps: the ranks' losses and gradients sum to the iteration's).  An image whose combined
     loss is not finite contributes exactly 0 to every gradient (the per-image loop's `continue`): its gradients are gated before they
     reach the scorer's backward and the camera-up head.  poses [B,4,4] on the device.  Returns (loss, the logged sums [3] = (sum of the
-    finite combined losses, their camera-up and score terms / gradient_accumulation_steps), finite [B]); nothing is read on the host."""
-    scores, up, n_host = id_module.forward_window(imgs, masks, rays_ori, rays_dirs, rays_rgb)
+    finite combined losses, their camera-up and score terms / gradient_accumulation_steps), finite [B]); nothing is read on the host.
+    ray_groups: the split of the scorer's backward over the rays (forward_window; 1 = unsplit, 0 = auto)."""
+    scores, up, n_host = id_module.forward_window(imgs, masks, rays_ori, rays_dirs, rays_rgb, ray_groups)
     target = torch.stack([ops.distance_target(rays_ori, rays_dirs, poses[i], n) for i, n in enumerate(n_host)])
 
     def terms(s, u):
@@ -106,12 +108,32 @@ def train_id_module(ckpt_path, device, id_module, rays_generator: Optional[Calla
                     scene_info, sequence_id, category_id, start_iterations: int = 0, renewal_every_n_iterations: int = 10,
                     display_every_n_iterations: int = 20, val_every_n_iterations: int = 20, n_iterations: int = 1500,
                     gradient_accumulation_steps: int = 32, lock_backbone: bool = True, log_fn: Optional[Callable[[str, float, int], None]] = None,
-                    batched_window: bool = False):
+                    batched_window: bool = False, data_parallel: bool = False, backward_ray_groups: int = 1):
     """batched_window: every iteration's gradient_accumulation_steps images go through ONE window (window_step_loss: one ray-MLP forward
     and backward instead of one per image, the image side as one batch, no host read before optimizer.step()) instead of the
-    reference's per-image loop.  Same image draw, loss, optimiser and checkpoint; needs lock_backbone (the backbone has no backward)."""
+    reference's per-image loop.  Same image draw, loss, optimiser and checkpoint; needs lock_backbone (the backbone has no backward).
+
+    data_parallel (needs batched_window; every rank of the process group calls this): the window of each iteration is split over the
+    ranks.  Rank 0 alone emits the rays and draws the images, with the random numbers of a single-rank run, and broadcasts both (the rays
+    at every renewal, the draw every iteration); rank r scores its block dd.shard_range(gradient_accumulation_steps, r, world) of the draw
+    against the full divisor, and dd.sum_gradients adds the ranks' gradients and logged sums in ONE all-reduce, after which every rank
+    steps its optimiser on the same bits (the parameters stay identical without a broadcast).  A rank whose window step raises
+    RuntimeError makes every rank raise together.  Evaluation and checkpoint stay on rank 0; the others wait in the next collective, on
+    the long-wait group.  Without a process group, or at world 1: the plain window.
+    backward_ray_groups: the split of the scorer's backward over the rays in the window (ops.score_backward: 1 = unsplit, 0 = auto)."""
+    from . import distributed as dd
+
     if batched_window and not lock_backbone:
         raise ValueError("batched_window=True needs lock_backbone=True: the batched image side runs the backbone without autograd")
+    if data_parallel and not batched_window:
+        raise ValueError("data_parallel=True needs batched_window=True: the ranks split the window of each iteration")
+    if int(backward_ray_groups) < 0:
+        raise ValueError(f"backward_ray_groups must be >= 0 (got {backward_ray_groups})")
+    dp = data_parallel and dd.is_dist() and dd.world() > 1
+    rank, world = (dd.rank(), dd.world()) if dp else (0, 1)
+    if dp and world > gradient_accumulation_steps:
+        raise ValueError(f"data_parallel=True over {world} ranks needs at least as many images per iteration (gradient_accumulation_steps = "
+                         f"{gradient_accumulation_steps})")
     from transformers.optimization import Adafactor        # the reference's optimiser (train.py:13,42-47), default arguments
 
     id_module.train()
@@ -120,8 +142,9 @@ def train_id_module(ckpt_path, device, id_module, rays_generator: Optional[Calla
         id_module.backbone_wrapper.eval()
     else:
         extra = list(id_module.backbone_wrapper.parameters())
-    optimizer = Adafactor(list(id_module.ray_preprocessor.parameters()) + list(id_module.attention.parameters())
-                          + list(id_module.camera_direction_prediction_network.parameters()) + extra)
+    params = (list(id_module.ray_preprocessor.parameters()) + list(id_module.attention.parameters())
+              + list(id_module.camera_direction_prediction_network.parameters()) + extra)
+    optimizer = Adafactor(params)
     loss_fn = DistanceBasedScoreLoss()
     writer = _writer()
     for k, v in (("ckpt_path", ckpt_path), ("category_id", category_id), ("sequence_id", sequence_id)):
@@ -139,15 +162,58 @@ def train_id_module(ckpt_path, device, id_module, rays_generator: Optional[Calla
         window_poses = torch.stack([gt_pose_and_intrinsics(c, device)[0] for c in scene_info.train_cameras]).to(device)
     rays_ori = rays_dirs = rays_rgb = None
     running_loss = 0.0
+    lo, hi = dd.shard_range(gradient_accumulation_steps, rank, world)
+    pending = None          # data-parallel rank 0: an exception of its own work between two collectives (emission, draw, evaluation)
     for iteration in range(start_iterations, n_iterations):
-        if iteration % renewal_every_n_iterations == 0:
-            rays_ori, rays_dirs, rays_rgb = rays_generator()
-        optimizer.zero_grad()
-        img_idx = torch.randint(0, len(scene_info.train_cameras), (gradient_accumulation_steps,), dtype=torch.long, device=device)
-        if batched_window:
+        renew = iteration % renewal_every_n_iterations == 0
+        if not dp:
+            if renew:
+                rays_ori, rays_dirs, rays_rgb = rays_generator()
+            optimizer.zero_grad()
+            img_idx = torch.randint(0, len(scene_info.train_cameras), (gradient_accumulation_steps,), dtype=torch.long, device=device)
+        else:
+            # rank 0 emits and draws (the random numbers of a single-rank run) and broadcasts [failure flag, draw]; then, at a renewal, the
+            # R x 9 floats of the rays (R first).  A failure of rank 0 reaches every rank through the flag: all raise at the same point.
+            ctl = torch.zeros(gradient_accumulation_steps + 1, dtype=torch.long, device=device)
+            if rank == 0 and pending is None:
+                try:
+                    fresh = torch.cat(rays_generator(), dim=-1) if renew else None
+                    ctl[1:] = torch.randint(0, len(scene_info.train_cameras), (gradient_accumulation_steps,), dtype=torch.long, device=device)
+                except Exception as e:  # noqa: BLE001 -- re-raised below, after the ranks have met
+                    pending = e
+            if rank == 0 and pending is not None:
+                ctl[0] = 1
+            ctl = dd.broadcast_tensor(ctl, 0, device, dtype=torch.long, shape=(gradient_accumulation_steps + 1,))
+            if int(ctl[0]):
+                if pending is not None:
+                    raise pending
+                raise RuntimeError(f"6dgs_amd: rank 0 failed before training iteration {iteration}; rank {rank} leaves the scene with it")
+            if renew:
+                rays = dd.broadcast_tensor(fresh if rank == 0 else None, 0, device)
+                rays_ori, rays_dirs, rays_rgb = (rays[:, i: i + 3].contiguous() for i in (0, 3, 6))
+            optimizer.zero_grad()
+            img_idx = ctl[1:]
+        if dp:
+            err = None
+            try:
+                idx = img_idx[lo:hi].tolist()
+                loss, logs, _ = window_step_loss(id_module, [window[i][0] for i in idx], [window[i][1] for i in idx], window_poses[img_idx[lo:hi]],
+                                                 rays_ori, rays_dirs, rays_rgb, model_up, gradient_accumulation_steps, backward_ray_groups)
+                loss.backward()
+            except Exception as e:      # noqa: BLE001 -- this rank contributes zeros and the flag; every rank raises after the reduce
+                err, logs = e, torch.zeros(3, device=device)
+            try:
+                logs = dd.sum_gradients(params, logs, failed=err is not None)
+            except RuntimeError:
+                if err is not None:                     # the failing rank re-raises its own exception, the others the peers' RuntimeError
+                    raise err
+                raise
+            optimizer.step()
+            acc_loss, acc_up, acc_score = logs.tolist()
+        elif batched_window:
             idx = img_idx.tolist()                                      # the draw on the host, once
             loss, logs, _ = window_step_loss(id_module, [window[i][0] for i in idx], [window[i][1] for i in idx], window_poses[img_idx],
-                                             rays_ori, rays_dirs, rays_rgb, model_up, gradient_accumulation_steps)
+                                             rays_ori, rays_dirs, rays_rgb, model_up, gradient_accumulation_steps, backward_ray_groups)
             loss.backward()
             optimizer.step()
             acc_loss, acc_up, acc_score = logs.tolist()                 # the logged scalars, read once per iteration
@@ -169,17 +235,25 @@ def train_id_module(ckpt_path, device, id_module, rays_generator: Optional[Calla
         log("train/loss_score", acc_score, iteration)
         running_loss += acc_loss
         if iteration % display_every_n_iterations == display_every_n_iterations - 1:
-            print(f"[{iteration}] loss: {running_loss / display_every_n_iterations}")
+            if rank == 0:
+                print(f"[{iteration}] loss: {running_loss / display_every_n_iterations}")
             running_loss = 0.0
-        if iteration % val_every_n_iterations == val_every_n_iterations - 1:
-            for split, cams in (("train", scene_info.train_cameras), ("val", scene_info.test_cameras)):
-                print(f"Eval on {'validation' if split == 'val' else split}...")
-                _, te, ae, sc, rc = test_pose_estimation(cams, id_module, rays_ori, rays_dirs, rays_rgb, model_up, sequence_id=sequence_id,
-                                                         category_id=category_id, loss_fn=loss_fn)
-                for tag, v in (("avg_translation_error", te), ("avg_angular_error", ae), ("avg_loss_score", sc), ("recall", rc)):
-                    log(f"{split}/{tag}", v, iteration)
+        if iteration % val_every_n_iterations == val_every_n_iterations - 1 and rank == 0:
+            try:
+                for split, cams in (("train", scene_info.train_cameras), ("val", scene_info.test_cameras)):
+                    print(f"Eval on {'validation' if split == 'val' else split}...")
+                    _, te, ae, sc, rc = test_pose_estimation(cams, id_module, rays_ori, rays_dirs, rays_rgb, model_up, sequence_id=sequence_id,
+                                                             category_id=category_id, loss_fn=loss_fn)
+                    for tag, v in (("avg_translation_error", te), ("avg_angular_error", ae), ("avg_loss_score", sc), ("recall", rc)):
+                        log(f"{split}/{tag}", v, iteration)
+            except Exception as e:      # noqa: BLE001 -- data-parallel, not the last iteration: the peers wait in the next broadcast
+                if not dp or iteration == n_iterations - 1:
+                    raise
+                pending = e
             id_module.train()
             if lock_backbone:
                 id_module.backbone_wrapper.eval()
+    if rank != 0:                                       # the checkpoint is rank 0's (the parameters are the same bits on every rank)
+        return
     torch.save({"epoch": n_iterations, "model_state_dict": id_module.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
                 "running_loss": running_loss}, ckpt_path)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SIXDGS_ABI_VERSION 8   /* 8: sixdgs_score_backward / sixdgs_score_backward_workspace_bytes (backward of the scorer for training); 7: sixdgs_image_prep (uint8 -> resized, cropped, normalised planar fp32 in one pass); 6: sixdgs_tok_pack / sixdgs_tok_linear (dense products of the backbone stage on packed weight planes, with LayerNorm / GELU / residual fusion), sixdgs_tok_attention, sixdgs_im2col, sixdgs_u8_to_planar; the three-plane bf16 key format and its scorer kernel removed (sixdgs_split_planes, sixdgs_key_planes_bytes gone; key planes exist as scaled fp16 only); 5: sixdgs_scorer_weights carries the composite layer w4k / b4k / m4k (k_proj folded into ray-MLP layer 4 on the key-cache path), sixdgs_select_begin / _sample_stats take h_n_tok (token packing of the select sweep); 4: the select path's slack derived from |q| |k| (sixdgs_key_planes_norm_max; q + d_key_norm_max arguments) and its ray-sharded form (sample_stats / prepare / topk_u, d_uk, allow_fewer), tile maxima of U (u_tile_max); 3: sixdgs_score_select + sixdgs_select_* stages (top-k without materialised logits); 2: plane-format scorer entry points, pass1/pass2, grid kNN, split-K, distance target */
+#define SIXDGS_ABI_VERSION 9   /* 9: sixdgs_score_backward_split / sixdgs_score_backward_split_workspace_bytes (the scorer backward split over ray groups); 8: sixdgs_score_backward / sixdgs_score_backward_workspace_bytes (backward of the scorer for training); 7: sixdgs_image_prep (uint8 -> resized, cropped, normalised planar fp32 in one pass); 6: sixdgs_tok_pack / sixdgs_tok_linear (dense products of the backbone stage on packed weight planes, with LayerNorm / GELU / residual fusion), sixdgs_tok_attention, sixdgs_im2col, sixdgs_u8_to_planar; the three-plane bf16 key format and its scorer kernel removed (sixdgs_split_planes, sixdgs_key_planes_bytes gone; key planes exist as scaled fp16 only); 5: sixdgs_scorer_weights carries the composite layer w4k / b4k / m4k (k_proj folded into ray-MLP layer 4 on the key-cache path), sixdgs_select_begin / _sample_stats take h_n_tok (token packing of the select sweep); 4: the select path's slack derived from |q| |k| (sixdgs_key_planes_norm_max; q + d_key_norm_max arguments) and its ray-sharded form (sample_stats / prepare / topk_u, d_uk, allow_fewer), tile maxima of U (u_tile_max); 3: sixdgs_score_select + sixdgs_select_* stages (top-k without materialised logits); 2: plane-format scorer entry points, pass1/pass2, grid kNN, split-K, distance target */
 #define SIXDGS_E_BADARG (-1)
 #define SIXDGS_E_WORKSPACE (-2)
 #define SIXDGS_E_UNSUPPORTED (-3)
@@ -332,6 +332,20 @@ int sixdgs_score_pass2(const float* row_stats, const int32_t* d_n_tok, int batch
 size_t sixdgs_score_backward_workspace_bytes(int batch);
 int sixdgs_score_backward(const float* q, const int32_t* d_n_tok, int batch, const float* key /*[R,384]*/, int64_t r,
                           const float* row_stats, const float* g, float* dq, float* dk, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
+/* sixdgs_score_backward with the rays of each 128-token tile split into ray_groups = G contiguous ranges of whole 128-ray tiles, so that
+ * 2 x B x G workgroups share the work of k_bwd_q's 2 x B (a small window -- a rank's share of a data-parallel iteration -- fills the GPU).
+ * Each group writes its partial softmax sums and c terms, then its partial dq, to the workspace; both are summed over g = 0 .. G-1 in that
+ * order (no atomics: the same inputs and G give the same bits; different G differ by rounding).  dk as in sixdgs_score_backward.
+ *   ray_groups = 1  k_bwd_q + k_bwd_k: the bits of sixdgs_score_backward (as does any G that resolves to 1: R <= 128 rays, B = 0)
+ *   ray_groups = 0  auto: G = ceil(CUs / (2 B)), so that the partial kernels cover every compute unit once
+ *   ray_groups < 0  SIXDGS_E_BADARG
+ * G is clamped to the number of 128-ray tiles and to 1024.  ws: sixdgs_score_backward_split_workspace_bytes(batch, r, ray_groups) bytes,
+ * 16-byte aligned: c and the sums (2 x B x 256 floats), the partial sums [G][B][256][2] and the partial dq [G][B][256][384] floats --
+ * G x B x 393 KB, about 50 MB with auto G on 256 CUs (2 x B x G = 256 workgroups x 128 rows x 384 floats) at any B. */
+size_t sixdgs_score_backward_split_workspace_bytes(int batch, int64_t r, int ray_groups);
+int sixdgs_score_backward_split(const float* q, const int32_t* d_n_tok, int batch, const float* key /*[R,384]*/, int64_t r,
+                                const float* row_stats, const float* g, float* dq, float* dk, int ray_groups, void* ws, size_t ws_bytes,
+                                sixdgs_stream_t stream);
 /* Top-k WITHOUT materialising the logits -- the inference path, where only idx/val are wanted (the reference driver reads nothing
  * else: test.py:105-107).  Needs the scaled fp16 key planes of ALL r rays (sixdgs_ray_keys_ex, SIXDGS_MMA_F16X3) and those of a
  * ray SAMPLE (any r_sample <= r rays of the same scene, e.g. one ray in 16, through the same entry point).  score[r] =
