@@ -256,6 +256,7 @@ class IdentificationModule(torch.nn.Module):
         defer_status (select path only): do NOT read the per-image status on the host here -- the call then enqueues work and
         nothing else (capturable in a hipGraph, no sync in the middle of a step) and leaves `self.pending_select`; the caller
         reads the status together with its own results (one D2H per batch) and calls `finish_select` if any image was refused."""
+        rays_to_output = ops.check_topk(rays_to_output)
         kc = self._ensure_keys(rays_ori, rays_dir, rays_rgb)
         w = self.packed_weights(rays_ori.device)
         q, n_tok, n_host = self._tokens_to_q(token_list, rays_ori.device)
@@ -263,7 +264,7 @@ class IdentificationModule(torch.nn.Module):
         self.pending_select = None
         capturing = torch.cuda.is_current_stream_capturing()
         if (not want_scores and kc.get("sample") is not None and ops.select_enabled() and ops.effective_mma_mode() in ops.F16_MODES
-                and rays_to_output <= ops.SELECT_MAX_CANDIDATES and (defer_status or not capturing)):
+                and rays_to_output <= ops.SELECT_MAX_CANDIDATES and (defer_status or not capturing)):     # (the candidate list must hold k)
             # inference: only the top-k is wanted -> no logits through HBM (sixdgs_score_select); images the bounds cannot decide
             # (status -1: too many near-ties for max_candidates, or an exponent overflow) go through the two-pass scorer below
             b, r = q.shape[0], rays_ori.shape[0]
@@ -326,12 +327,13 @@ class IdentificationModule(torch.nn.Module):
         top-k is wanted and every rank has a ray sample; images it cannot decide, and use_select=False, take the two-pass cut
         (distributed.score_topk_ray_sharded).  Returns (global idx [B,k], val [B,k]) identical on every rank."""
         from . import distributed as dd
-        dev, k = rays_ori.device, rays_to_output
+        dev, k = rays_ori.device, ops.check_topk(rays_to_output)
         world = dd.world()
         kc = self._ensure_keys(rays_ori, rays_dir, rays_rgb, sample_min_rays=max(4096, ops.SELECT_MIN_RAYS // max(world, 1)))
         q, n_tok, n_host = self._tokens_to_q(token_list, dev)
         f16 = ops.effective_mma_mode() in ops.F16_MODES
-        have = torch.tensor([1 if (kc.get("sample") is not None and f16 and use_select and ops.select_enabled() and k <= ops.SELECT_MAX_CANDIDATES) else 0,
+        have = torch.tensor([1 if (kc.get("sample") is not None and f16 and use_select and ops.select_enabled()
+                                  and k <= ops.SELECT_MAX_CANDIDATES) else 0,        # (the candidate list must hold k)
                              0 if kc.get("sample") is None else int(kc["sample"][0].shape[0])], dtype=torch.int64, device=dev)
         if dd.is_dist():
             flag, cnt = have[:1].clone(), have[1:].clone()
@@ -369,6 +371,7 @@ class IdentificationModule(torch.nn.Module):
         sweep 2, so only the remaining chunks pay the ray MLP twice.  Same result as score_tokens up to the rounding of the sum
         of exponentials.  Returns (idx [B,k], val [B,k]); no [B,R] score vector.  return_stats: also (global row statistics
         [B,256,2], softmax mass per image = sum of all scores, which must equal the image's token count)."""
+        rays_to_output = ops.check_topk(rays_to_output)
         dev = rays_ori.device
         w = self.packed_weights(dev)
         q, n_tok, n_host = self._tokens_to_q(token_list, dev)
@@ -378,7 +381,7 @@ class IdentificationModule(torch.nn.Module):
         f16 = planes_mode = mode in ops.F16_MODES
         self.last_scoring_path = "streamed two-pass"
         if (f16 and use_select and not return_stats and ops.select_enabled() and r >= ops.SELECT_MIN_RAYS and k <= ops.SELECT_MAX_CANDIDATES
-                and not torch.cuda.is_current_stream_capturing()):
+                and not torch.cuda.is_current_stream_capturing()):      # (k <= SELECT_MAX_CANDIDATES: the candidate list must hold k)
             # Select path, streamed: ONE sweep of ray MLP + matrix-core pass over the chunks (plus 1/16 for the sample) instead
             # of two -- U (4 B per ray and image) is all that is kept of a chunk; the candidates' keys are recomputed at the end.
             cmax = ops.SELECT_MAX_CANDIDATES
@@ -489,6 +492,7 @@ class IdentificationModule(torch.nn.Module):
     def test_images(self, imgs, masks, rays_ori, rays_dir, rays_rgb, rays_to_output: int = 100, want_scores: bool = True,
                     workspace: Optional[torch.Tensor] = None, images_in_flight: Optional[int] = None):
         """Batched test_image: returns dict(idx[B,k], values[B,k], scores[B,R]|None, camera_up_dir[B,3], n_tokens[B])."""
+        rays_to_output = ops.check_topk(rays_to_output)          # before the image side runs
         toks, fmaps = self.image_tokens(imgs, masks)
         up = self.camera_up(fmaps)
         idx, val, scores = self.score_tokens(toks, rays_ori, rays_dir, rays_rgb, rays_to_output, want_scores, workspace,

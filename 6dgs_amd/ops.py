@@ -752,8 +752,19 @@ def score_topk(q: torch.Tensor, n_tok: torch.Tensor, key: Optional[torch.Tensor]
     return idx, val, scores, stats
 
 
+MAX_TOPK = 1024                  # the largest k any top-k entry point takes (the C checks: topk <= 1024, one workgroup sorts the list)
+
+
+def check_topk(k, what: str = "rays_to_output") -> int:
+    """k as an int in [1, MAX_TOPK], or ValueError -- for callers that must refuse before any GPU work is enqueued."""
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_TOPK:
+        raise ValueError(f"6dgs_amd: {what} = {k!r}: the top-k takes 1 <= k <= MAX_TOPK = {MAX_TOPK}")
+    return int(k)
+
+
 SELECT_MAX_CANDIDATES = 4096     # candidates re-scored exactly per image; an image with more falls back to the two-pass scorer
-SELECT_SAMPLE_STRIDE = 16        # the pre-pass sees one ray in 16 ...
+#                                  (a candidate budget, not a top-k limit: the select path needs room for k of them, k <= MAX_TOPK)
+SELECT_SAMPLE_STRIDE = 16       # the pre-pass sees one ray in 16 ...
 SELECT_SAMPLE_STRIDE_LARGE = 32  # ... one in 32 from SELECT_LARGE_RAYS rays (the sample is then still >= 0.5 M rays: its row sums are
 SELECT_LARGE_RAYS = 16_000_000   # as representative as one in 16 of a scene half the size, and the pre-pass costs half) ...
 SELECT_SAMPLE_STRIDE_HUGE = 64   # ... one in 64 from SELECT_HUGE_RAYS rays (>= 0.5 M sample rays again).  The sample only sets the
