@@ -7,6 +7,7 @@
 #include "device_math.h"
 #include "sweep_plan.h"
 #include "dense_layout.h"
+#include "sweep_layout.h"
 using namespace sdg;
 
 extern "C" {
@@ -160,6 +161,22 @@ int hc_sweep_pack(const int* h_n_tok, int batch, int cap, int* out, int max_laun
   }
   return (int)plan.size();
 }
+// ---- sweep_layout.h: the select sweep on 16x16x32 MFMAs (tests/test_sweep_layout.py walks every lane and register through them) ----
+int hc_sw_const(int which) {
+  const int v[] = {sw::kTokBlocks, sw::kRayBlocks, sw::kBlockBytes, sw::kBflySteps};
+  return which >= 0 && which < 4 ? v[which] : -1;
+}
+int hc_sw_frag_row(int lane) { return sw::frag_row(lane); }
+int hc_sw_frag_chunk(int lane, int plane) { return sw::frag_chunk(lane, plane); }
+unsigned hc_sw_frag_offset(int row0, int lane, int plane) { return sw::frag_offset(row0, lane, plane); }
+int hc_sw_acc_token(int lane, int tb) { return sw::acc_token(lane, tb); }
+int hc_sw_acc_ray(int lane, int rb, int reg) { return sw::acc_ray(lane, rb, reg); }
+int hc_sw_bfly_partner(int lane, int step) { return sw::bfly_partner(lane, step); }
+int hc_sw_bfly_keeps(int lane, int step, int i) { return sw::bfly_keeps(lane, step, i) ? 1 : 0; }
+int hc_sw_out_index(int lane, int x) { return sw::out_index(lane, x); }
+int hc_sw_out_ray(int lane, int x) { return sw::out_ray(lane, x); }
+int hc_sw_part_writes(int lane) { return sw::part_writes(lane) ? 1 : 0; }
+int hc_sw_part_row(int wn, int lane) { return sw::part_row(wn, lane); }
 int hc_dl_const(int which) {
   const int v[] = {dl::kSlabB, dl::kPRow, dl::kGran, dl::kGranSlab, dl::kChunkRun};
   return which >= 0 && which < 5 ? v[which] : -1;

@@ -19,6 +19,7 @@
 #include <cstdio>
 #include "gemm_kernel.h"
 #include "sweep_plan.h"
+#include "sweep_layout.h"
 
 using namespace sdg;
 
@@ -231,11 +232,25 @@ constexpr int kQStageX = 256 * 64;       // one plane of one stage
 constexpr int kKBaseX = 4 * kQStageX;    // 64 KiB
 constexpr int kLdsX = kKBaseX + 6 * kQStageX;   // 160 KiB
 
+// MFMA shape of the tile's matrix work.  Same cycles per FLOP; the chip holds a higher clock on the 16x16x32 form (profiles/sweep_mfma_16x16x32.md).
+constexpr int kMfma32 = 0;     // v_mfma_f32_32x32x16_f16: a wave's 64 tokens x 128 rays are 2 x 4 blocks, a 32-k slab is two k-steps
+constexpr int kMfma16 = 1;     // v_mfma_f32_16x16x32_f16: 4 x 8 blocks, a slab is ONE k-step (the select sweep only; lane maps: sweep_layout.h)
+
 // TERMS: kAllTerms or kOneTerm.  OUT: what leaves the kernel (kOut*): fp32 or 24-bit fixed-point logits (see kTileBytes24),
-// statistics only, or the upper-bound column sums of the select path
-template <int TERMS, int OUT, bool PERS = false>
+// statistics only, or the upper-bound column sums of the select path.  SHAPE: kMfma32, or kMfma16 (OUT == kOutUB only: the blocked logits of the
+// two-pass outputs ARE the 32x32 accumulator layout).
+//
+// The kMfma16 tile.  Same workgroup tile, rings, LDS image and DMA pieces; per slab a wave runs 8 steps, one per 16-ray block rb, of 12 MFMAs
+// (l*h, h*l, h*h for the 4 token blocks).  The 4 x 2 token fragments stay in registers for the whole slab (32), of the ray fragments the h plane is
+// double buffered and the l plane, which only the middle term uses, is not (3 x 4): 44 fragment registers and the minimum of 24 ds_read_b128 per slab.  The slab barrier sits before step 7, whose slots
+// carry the next slab's first ray block and, plane by plane as the step's MFMAs release them (the l planes after the l*h term, the h plane of
+// token block i after its h*h), the next slab's token fragments; only those last 4 reads are still in flight when the next slab starts, and
+// its first 4 MFMAs do not need them (counted lgkmcnt).  The 8 DMA pieces of a batch -- q of slab + 1, key of slab + 2 -- go into steps 0 and 1.
+template <int TERMS, int OUT, bool PERS = false, int SHAPE = kMfma32>
 __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
   static_assert(TERMS == kAllTerms || TERMS == kOneTerm, "k_logits_f16x: TERMS is 3 or 1");
+  static_assert(SHAPE == kMfma32 || (SHAPE == kMfma16 && OUT == kOutUB && TERMS == kAllTerms), "k_logits_f16x: 16x16x32 is the select sweep's shape");
+  constexpr bool S16 = SHAPE == kMfma16;
   constexpr bool L24 = OUT == kOutL24;
   constexpr bool one_term = TERMS == kOneTerm;
   __shared__ __attribute__((aligned(1024))) char lds[kLdsX];
@@ -250,7 +265,11 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
   const float cq = A.q_quarter_scales ? A.qinv[4 * b + wm] : A.qinv[2 * b + (wm >> 1)];
   const bool active = wm * 64 < M;
   float ct[2] = {0.f, 0.f};
-  if (OUT == kOutUB) {
+  float ct16[sw::kTokBlocks] = {0.f, 0.f, 0.f, 0.f};
+  if (S16) {
+#pragma unroll
+    for (int tb = 0; tb < sw::kTokBlocks; ++tb) ct16[tb] = A.ctok[(int64_t)b * kT + wm * 64 + sw::acc_token(lane, tb)];
+  } else if (OUT == kOutUB) {
     ct[0] = A.ctok[(int64_t)b * kT + wm * 64 + (lane & 31)];
     ct[1] = A.ctok[(int64_t)b * kT + wm * 64 + 32 + (lane & 31)];
   }
@@ -264,6 +283,7 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
   float m_run[2] = {-INFINITY, -INFINITY}, s_run[2] = {0.f, 0.f};
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   f32x2 zs[2][2] = {{{0.f, 0.f}, {0.f, 0.f}}, {{0.f, 0.f}, {0.f, 0.f}}};      // [token block][r & 2]: pairs (r & 3) = (0, 1), (2, 3)
+  float zs16[sw::kTokBlocks] = {0.f, 0.f, 0.f, 0.f};      // kMfma16: [token block] (one register each: the tile sits on the 256-register line)
   const int t_begin = grp * t_base + min(grp, t_rem);
   const int t_end = t_begin + t_base + (grp < t_rem ? 1 : 0);
   if (PERS && !(M > 0) && A.sib_sync && t_begin < t_end) {      // an image without tokens walks no tiles: its arrivals all at once
@@ -303,7 +323,9 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
                                        (lds_ptr_t)(lds + qstage * (2 * kQStageX) + (wave * 4 + i) * 1024), 16, 0, 0);
     };
     auto issue_k = [&](const char* kbase, int lim, const int s, const int kstage, const int i) {
-      const unsigned ob = (unsigned)min(rowK[i], lim) * kRowF + offK[i] + (unsigned)(s * kSlabF);
+      // (kMfma16 keeps 3 of these 8 registers: the swizzle term of piece i depends on i & 1 alone, and the rows are 8 apart)
+      const unsigned ob = S16 ? (unsigned)min(rowK[0] + 8 * i, lim) * kRowF + offK[i & 1] + (unsigned)(s * kSlabF)
+                              : (unsigned)min(rowK[i], lim) * kRowF + offK[i] + (unsigned)(s * kSlabF);
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(kbase + ob),
                                        (lds_ptr_t)(lds + kKBaseX + kstage * (2 * kQStageX) + (wave * 4 + i) * 1024), 16, 0, 2);
     };
@@ -331,6 +353,23 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
       const int off = kstage * (2 * kQStageX) + t * 4096;
       return off < 65536 ? lds_read_frag_h_off(fb[ks][pl], off & 65535) : lds_read_frag_h_off(fb2[ks][pl], off & 65535);
     };
+    // kMfma16 (sweep_layout.h): one address per plane; a 16-row block adds 2048 B, which with the stage still fits the offset field
+    unsigned ga[2] = {0u, 0u}, gb[2] = {0u, 0u}, gb2[2] = {0u, 0u};
+    if (S16) {
+#pragma unroll
+      for (int pl = 0; pl < 2; ++pl) {
+        ga[pl] = lds0 + sw::frag_offset(wm * 64, lane_p, pl);
+        gb[pl] = lds0 + kKBaseX + sw::frag_offset(wn * 128, lane_p, pl);
+        gb2[pl] = gb[pl] + 65536u;
+      }
+    }
+    auto read_a16 = [&](const int tb, const int pl, const int qstage) {
+      return lds_read_frag_h_off(ga[pl], qstage * (2 * kQStageX) + tb * sw::kBlockBytes);
+    };
+    auto read_b16 = [&](const int rb, const int pl, const int kstage) {
+      const int off = kstage * (2 * kQStageX) + rb * sw::kBlockBytes;
+      return off < 65536 ? lds_read_frag_h_off(gb[pl], off & 65535) : lds_read_frag_h_off(gb2[pl], off & 65535);
+    };
     // logits of image bl, blocked by 128-ray tiles: [tile128][token group g = t / 32][ray quad][t % 32][r % 4]
     float* lg = A.logits + (int64_t)bl * kT * A.ldl + ((wm * 2) * 4096 + lane_p * 4);
     char* lg24 = reinterpret_cast<char*>(A.logits) + (int64_t)bl * kT * A.ldl * 4;   // same per-image region, 24-bit layout
@@ -338,17 +377,30 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
     int lim_cur = tile_lim(t_begin);
 
     f16x8 a0[2][2], a1[2][2], b0[2][2], b1[2][2];   // [row block][plane]
+    f16x8 tq[sw::kTokBlocks][2], kh[2], kl;         // kMfma16: token fragments [block][plane] of the slab; ray fragments of a step: plane h [buffer], plane l
     auto wait_lds = [&]() {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
     };
     // ---- prologue: key slabs 0, 1, 2 and q slabs 0, 1 in the steady-state order (q of a batch before its key) ----------
+    // (kMfma16: key 0, q 0, key 1 -- slab 0 itself issues the batch q 1, key 2, as it does in every later tile)
 #pragma unroll
     for (int i = 0; i < 4; ++i) issue_k(kcur, lim_cur, 0, 0, i);
 #pragma unroll
     for (int i = 0; i < 4; ++i) issue_q(0, 0, i);
 #pragma unroll
     for (int i = 0; i < 4; ++i) issue_k(kcur, lim_cur, 1, 1, i);
+    if (S16) {
+      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+#pragma unroll
+      for (int pl = 0; pl < 2; ++pl) {
+#pragma unroll
+        for (int tb = 0; tb < sw::kTokBlocks; ++tb) tq[tb][pl] = read_a16(tb, pl, 0);
+      }
+      kh[0] = read_b16(0, 0, 0);
+      kl = read_b16(0, 1, 0);
+    } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) issue_q(1, 1, i);
 #pragma unroll
@@ -363,6 +415,7 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
         a0[t][pl] = read_a(t, 0, pl, 0);
         b0[t][pl] = read_b(t, 0, pl, 0);
       }
+    }
     wait_lds();
 
     for (int tile = t_begin; tile < t_end; ++tile) {
@@ -372,12 +425,33 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
       const char* knext = has_next ? kcur + (int64_t)kBNX * kRowF : kcur;
       const int lim_next = has_next ? tile_lim(tile + 1) : lim_cur;
       // the 12 slabs are fully unrolled; keep the per-slab source addresses from being hoisted out of the tile loop
-      asm volatile("" : "+v"(offQ[0]), "+v"(offQ[1]), "+v"(offQ[2]), "+v"(offQ[3]), "+v"(offK[0]), "+v"(offK[1]), "+v"(offK[2]), "+v"(offK[3]));
+      if (S16) asm volatile("" : "+v"(offQ[0]), "+v"(offQ[1]), "+v"(offQ[2]), "+v"(offQ[3]), "+v"(offK[0]), "+v"(offK[1]));
+      else asm volatile("" : "+v"(offQ[0]), "+v"(offQ[1]), "+v"(offQ[2]), "+v"(offQ[3]), "+v"(offK[0]), "+v"(offK[1]), "+v"(offK[2]), "+v"(offK[3]));
       // ---- token-aware (round 4): a wave whose 64-token row block lies at or beyond the image's token count (masked Tanks&Temples / Blender views
       // keep 56-140 of 256 tokens, backbone.py:86-114) has nothing to compute: it skips the tile's 576 MFMAs, fragment reads and accumulators and only
       // does its share of the workgroup's data movement -- per slab the same counted wait, the same barrier and the same 8 DMA pieces in the same
       // order as the waves that compute (vmcnt bookkeeping unchanged), issued right behind the barrier.  Wave-uniform branch; waves 0-3 (token rows
       // 0-127) sit on the four SIMDs, so an image of <= 128 tokens leaves every SIMD with ONE computing wave and half the matrix work.
+      if (S16 && !active) {                          // kMfma16: the batch of slab sl (q sl + 1, key sl + 2) goes BEFORE the slab's wait and barrier
+        int kst = 2;                                 // (sl + 2) % 3
+#pragma unroll 1
+        for (int sl = 0; sl < 12; ++sl) {
+          const int sq = sl + 1 < 12 ? sl + 1 : 0;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) issue_q(sq, sq & 1, i);
+          const bool nxt = sl + 2 >= 12;
+          const char* kb = nxt ? knext : kcur;
+          const int kl = nxt ? lim_next : lim_cur, sk = nxt ? sl + 2 - 12 : sl + 2;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) issue_k(kb, kl, sk, kst, i);
+          kst = kst == 2 ? 0 : kst + 1;
+          asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+          __builtin_amdgcn_s_barrier();
+        }
+        kcur = knext;
+        lim_cur = lim_next;
+        continue;
+      }
       if (!active) {
         int ks3 = 0;                                 // sl % 3 (a ROLLED loop with run-time stages: unrolled, its 96 piece addresses cost the computing
 #pragma unroll 1                                     // waves registers -- 41 spilled VGPRs in the first build)
@@ -425,6 +499,66 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
         }
       };
 
+      typedef float f32x4 __attribute__((ext_vector_type(4)));
+      f32x4 acc16[sw::kTokBlocks][sw::kRayBlocks];
+      if (S16) {
+#pragma unroll
+        for (int i = 0; i < sw::kTokBlocks; ++i)
+#pragma unroll
+          for (int j = 0; j < sw::kRayBlocks; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // One step: ray block rb against the slab's 4 token blocks, term by term (l*h, h*l, h*h: smallest first per accumulator, and 4 MFMAs
+        // between two on the same accumulator); `side(slot)` places at most one read or DMA piece behind each MFMA.
+        auto step16 = [&](f16x8& xh, const int rb, auto side) {
+          constexpr int PQ[3] = {1, 0, 0};      // token plane and (below) ray plane of a term: 0 = h, 1 = l
+#pragma unroll
+          for (int q = 0; q < 3; ++q) {
+#pragma unroll
+            for (int tb = 0; tb < sw::kTokBlocks; ++tb) {
+              acc16[tb][rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q == 1 ? kl : xh, tq[tb][PQ[q]], acc16[tb][rb], 0, 0, 0);
+              side(q * 4 + tb);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
+        };
+#pragma unroll
+        for (int sl = 0; sl < 12; ++sl) {
+          const int qs1 = (sl + 1) & 1, kn = (sl + 1) % 3, ks2 = (sl + 2) % 3, ks3 = sl % 3;
+#pragma unroll
+          for (int rb = 0; rb < sw::kRayBlocks - 1; ++rb) {
+            // steps 0..6: read ray block rb + 1 into the other buffer; step 0 first lets the 4 token h planes land that the previous slab's last
+            // step left in flight (its slots 0..3 are the l*h term: token l planes); steps 0 and 1 carry the batch q(sl + 1) -> the q stage and
+            // key(sl + 2) -> the key stage that slab sl - 1 left behind its barrier
+            step16(kh[rb & 1], rb, [&](const int slot) {
+              if (rb == 0 && slot == 3) wait_lds();
+              if (slot == 4) kh[(rb + 1) & 1] = read_b16(rb + 1, 0, ks3);
+              if (slot == 8) kl = read_b16(rb + 1, 1, ks3);      // (the l plane has one buffer: the h*l term, slots 4..7, was its last use)
+              if (rb == 0 && slot >= 6 && slot < 10) issue_q((sl + 1) % 12, qs1, slot - 6);
+              if (rb == 1 && slot >= 6 && slot < 10) {
+                if (sl + 2 < 12) issue_k(kcur, lim_cur, sl + 2, ks2, slot - 6);
+                else issue_k(knext, lim_next, sl + 2 - 12, ks2, slot - 6);
+              }
+            });
+            wait_lds();
+          }
+          // q(sl + 1) was issued before key(sl + 2): only those 4 key pieces are younger.  After the barrier slab sl + 1 is visible to every
+          // wave; every wave has read the last fragment of slab sl (ray block 7, during step 6).
+          asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+          __builtin_amdgcn_s_barrier();
+          // step 7: the first ray block of slab sl + 1, then its token fragments as this step's terms release their registers
+          step16(kh[1], sw::kRayBlocks - 1, [&](const int slot) {
+            if (slot == 0) kh[0] = read_b16(0, 0, kn);
+            else if (slot >= 4 && slot < 8) tq[slot - 4][1] = read_a16(slot - 4, 1, qs1);
+            if (slot == 8) kl = read_b16(0, 1, kn);      // (before the 4 reads that may stay in flight)
+            if (slot >= 8) tq[slot - 8][0] = read_a16(slot - 8, 0, qs1);
+          });
+          if (sl < 11) {      // the 4 h planes may still be in flight: step 0 waits for them behind its 4th MFMA
+            asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+          } else {
+            wait_lds();       // the tile's last slab: everything lands before the epilogue
+          }
+        }
+      } else {
 #pragma unroll
       for (int sl = 0; sl < 12; ++sl) {
         const int qs = sl & 1, ks3 = sl % 3;              // stages of this slab
@@ -466,6 +600,7 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
         });
         wait_lds();
       }
+      }
 
       // ---- sibling lock-step: the nb workgroups of this sibling set (same XCD: consecutive work items of the remap) meet here after
       // every sib_period-th tile (and after a group's last one), so that they stay within a fraction of a tile of each other and the key slabs one of them pulls from HBM are still in the XCD's
@@ -502,7 +637,71 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
         // by a halving butterfly over the 32 lanes of each half wave (lane bit i <-> ray-register bit 3 - i, DPP for the two
         // in-quad steps, ds_swizzle for the rest) and leave as TWO 4-byte stores per lane and tile: ray
         // 64 b4 + 32 x + 8 rg + 4 h + j of the wave's 128-ray half with 4 rg + j = bitrev4(lane & 15), h = lane >> 5.
-        if (active) {
+        if (S16) {
+          // kMfma16 (maps: sweep_layout.h).  A lane holds ONE token of each of its 4 token blocks and, per ray block, the 4 rays 4 (lane >> 4) + reg:
+          // per ray the 4 token blocks add up in registers, then the 32 values v[4 rb + reg] go through a halving butterfly over the 16 token lanes --
+          // lane bit s <-> index bit s; the two register bits (DPP) as soon as a ray block is done, the two ray-block bits (ds_swizzle) at the end --
+          // and leave as TWO 4-byte stores per lane and tile, 64 consecutive rays per wave instruction.  Same operations per e' as the 32x32 epilogue.
+          const int t128 = min(2 * tile + wn, n_tiles128 - 1);
+          const float cfl = ((cq * load_uniform(A.kinv + t128)) * kInvSqrtD) * 1.4426950408889634f;
+          const bool ragged = lim_cur < kBNX - 1;
+          int le = lane_p;      // (an opaque copy per tile: as loop invariants the lane masks, the 16 ray indices of the ragged mask and the store
+          asm volatile("" : "+v"(le));      // offsets were hoisted out of the tile and group loops and spilled)
+          const int ray0 = wn * 128 + sw::acc_ray(le, 0, 0);
+          const bool lb0 = le & 1, lb1 = le & 2, lb2 = le & 4, lb3 = le & 8;
+          const f32x2 cfl2 = {cfl, cfl};
+          f32x2 ct2[sw::kTokBlocks];      // (the pairs are formed per tile from opaque copies: hoisted, they were 8 registers live across the slab loop)
+#pragma unroll
+          for (int tb = 0; tb < sw::kTokBlocks; ++tb) {
+            float c = ct16[tb];
+            asm volatile("" : "+v"(c));
+            ct2[tb] = f32x2{c, c};
+          }
+          float w8[sw::kRayBlocks];
+#pragma unroll
+          for (int rb = 0; rb < sw::kRayBlocks; ++rb) {
+            float u[4];
+#pragma unroll
+            for (int r = 0; r < 4; r += 2) {
+              f32x2 e[sw::kTokBlocks];
+#pragma unroll
+              for (int tb = 0; tb < sw::kTokBlocks; ++tb) {
+                const f32x2 x = __builtin_elementwise_fma(f32x2{acc16[tb][rb][r], acc16[tb][rb][r + 1]}, cfl2, ct2[tb]);
+                e[tb] = f32x2{__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
+                if (ragged) {
+                  const int rr = ray0 + sw::acc_ray(0, rb, r);                            // clamped duplicates of the last ray count as 0
+                  e[tb] = f32x2{rr <= lim_cur ? e[tb].x : 0.f, rr + 1 <= lim_cur ? e[tb].y : 0.f};
+                }
+                zs16[tb] += e[tb].x + e[tb].y;
+              }
+              const f32x2 uu = (e[0] + e[1]) + (e[2] + e[3]);
+              u[r] = uu.x;
+              u[r + 1] = uu.y;
+            }
+            float v2[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+              const float keep = lb0 ? u[2 * i + 1] : u[2 * i], send = lb0 ? u[2 * i] : u[2 * i + 1];
+              v2[i] = keep + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+            }
+            const float keep = lb1 ? v2[1] : v2[0], send = lb1 ? v2[0] : v2[1];
+            w8[rb] = keep + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+          }
+          float w4[4], o[2];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float keep = lb2 ? w8[2 * i + 1] : w8[2 * i], send = lb2 ? w8[2 * i] : w8[2 * i + 1];
+            w4[i] = keep + __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, send), 0x101F));   // lane ^ 4
+          }
+#pragma unroll
+          for (int x = 0; x < 2; ++x) {
+            const float keep = lb3 ? w4[2 * x + 1] : w4[2 * x], send = lb3 ? w4[2 * x] : w4[2 * x + 1];
+            o[x] = keep + __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, send), 0x201F));    // lane ^ 8
+          }
+          float* up = A.ub + ((int64_t)bl * 4 + wm) * A.ub_stride + ((int64_t)tile * kBNX + wn * 128);
+          __builtin_nontemporal_store(o[0], up + sw::out_ray(le, 0));
+          __builtin_nontemporal_store(o[1], up + sw::out_ray(le, 1));
+        } else if (active) {
           const int t128 = min(2 * tile + wn, n_tiles128 - 1);
           const float cfl = ((cq * load_uniform(A.kinv + t128)) * kInvSqrtD) * 1.4426950408889634f;
           const bool ragged = lim_cur < kBNX - 1;
@@ -643,6 +842,20 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
   // merge the four partials of every token (2 ray halves of the lane layout x 2 waves wn) through the (now idle) ring
   __syncthreads();
   float(*part)[256][2] = reinterpret_cast<float(*)[256][2]>(lds);   // [wn * 2 + (lane >> 5)][token][max, sum]
+  if (S16) {      // four lane groups per token: the pairs (lane, lane ^ 16) add up in the wave, which leaves the buffer's four rows per token
+    int lm = lane;
+    if (PERS) asm volatile("" : "+v"(lm));      // (formed per group, like lane_p)
+#pragma unroll
+    for (int tb = 0; tb < sw::kTokBlocks; ++tb) {
+      float z = zs16[tb];
+      z += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, z), 0x401F));      // lane ^ 16
+      if (sw::part_writes(lm)) {
+        float* pp = part[sw::part_row(wn, lm)][wm * 64 + sw::acc_token(lm, tb)];
+        pp[0] = 0.f;
+        pp[1] = z;
+      }
+    }
+  } else {
 #pragma unroll
   for (int tm = 0; tm < 2; ++tm) {
     float* pp = part[wn * 2 + (lane >> 5)][wm * 64 + tm * 32 + (lane & 31)];
@@ -653,6 +866,7 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
       pp[0] = m_run[tm];
       pp[1] = s_run[tm];
     }
+  }
   }
   __syncthreads();
   if (tid < 256) {
@@ -2061,6 +2275,12 @@ int sibling_sync_mode() {      // 0 one-shot grid, 1 persistent sibling sets in 
   }
   return mode;
 }
+// MFMA shape of the select sweep: 16x16x32 (default), or SIXDGS_SWEEP_MFMA=32 for the 32x32x16 form (developer switch: the A/B of
+// profiles/sweep_mfma_16x16x32.md and what tests/test_gpu_sweep_shape.py compares against; read at every launch, so a test can flip it)
+bool sweep_mfma16() {
+  const char* e = getenv("SIXDGS_SWEEP_MFMA");
+  return !(e && atoi(e) == 32);
+}
 int sibling_sync_cus() {
   static int cus = -1;
   if (cus < 0) {
@@ -2242,7 +2462,8 @@ int sixdgs_select_sweep(const float* q, const int32_t* d_n_tok, const int32_t* h
         grid = (unsigned)(V.n_sets * ns);
       }
       SdgProfileScope scope(prof, s, 2.0 * tok * SIXDGS_D * (double)r, (double)r * (kRowF + T.n_images * 16.0));
-      auto kern = V.n_sets > 0 ? k_logits_f16x<kAllTerms, kOutUB, true> : k_logits_f16x<kAllTerms, kOutUB, false>;
+      auto kern = sweep_mfma16() ? (V.n_sets > 0 ? k_logits_f16x<kAllTerms, kOutUB, true, kMfma16> : k_logits_f16x<kAllTerms, kOutUB, false, kMfma16>)
+                                 : (V.n_sets > 0 ? k_logits_f16x<kAllTerms, kOutUB, true> : k_logits_f16x<kAllTerms, kOutUB, false>);
       hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, s, V);
     }
     hipLaunchKernelGGL(k_merge_stats_slots, dim3((unsigned)T.n_images, 4), dim3(1024), 0, s, w.partial, n_groups, T, (float*)nullptr, gsum);
