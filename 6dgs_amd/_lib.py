@@ -22,7 +22,7 @@ sz = C.c_size_t
 
 
 PROFILE_SLOTS = 128
-ABI_VERSION = 9          # must equal SIXDGS_ABI_VERSION in include/sixdgs.h (checked by __graft_entry__.post_build_checks)
+ABI_VERSION = 10         # must equal SIXDGS_ABI_VERSION in include/sixdgs.h (checked by __graft_entry__.post_build_checks)
 
 
 class Profile(C.Structure):
@@ -51,6 +51,8 @@ SIGNATURES = {
     "sixdgs_rotate_isocell": (i32, [vp, i64, vp, i64, vp, vp]),
     "sixdgs_emit_isocell": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp]),
     "sixdgs_eval_sh_color": (i32, [vp, i32, vp, i64, i32, vp, vp]),
+    "sixdgs_splat_views_workspace_bytes": (sz, [i64, i32, i32, i32]),
+    "sixdgs_splat_views": (i32, [vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, sz, vp]),
     "sixdgs_packed_weights_floats": (sz, []),
     "sixdgs_pack_weights": (i32, [vp] * 13 + [C.POINTER(ScorerWeights), vp]),
     "sixdgs_ray_encode": (i32, [vp, vp, vp, i64, vp, vp]),

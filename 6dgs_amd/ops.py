@@ -287,6 +287,50 @@ def eval_sh_color(sh: torch.Tensor, dirs: torch.Tensor, sh_degree: int) -> torch
     return out
 
 
+def splat_views_workspace_bytes(n: int, views: int, width: int, height: int) -> int:
+    return int(_lib.load().sixdgs_splat_views_workspace_bytes(int(n), int(views), int(width), int(height)))
+
+
+@_on_device
+def splat_views(xyz, scale, f_dc, f_rest, sh_degree: int, cams: torch.Tensor, width: int, height: int, channels: int = 3,
+                extent: float = 1.0, near_z: float = 0.05, background=(1.0, 1.0, 1.0), want_winner: bool = False,
+                scale_is_log: bool = True, workspace: Optional[torch.Tensor] = None):
+    """Synthetic query views: the Gaussians as z-buffered flat discs in their SH colour towards the camera (sixdgs_splat_views in
+    include/sixdgs.h defines the image pixel by pixel).  cams [V,16] = w2c rows 0..2 (12 floats), fx, fy, cx, cy per view.
+    Returns the uint8 image [V,height,width,channels], and with want_winner (image, winner int32 [V,height,width], -1 = background)."""
+    if channels not in (3, 4):
+        raise ValueError(f"channels must be 3 or 4 (got {channels})")
+    if not (float(extent) > 0.0 and float(extent) < float("inf")):
+        raise ValueError(f"extent must be positive and finite (got {extent})")
+    if not float(near_z) >= 0.0:
+        raise ValueError(f"near_z must be >= 0 (got {near_z})")
+    if int(width) < 1 or int(height) < 1:
+        raise ValueError(f"width and height must be positive (got {width} x {height})")
+    if not torch.is_tensor(cams) or cams.dim() != 2 or cams.shape[1] != 16:
+        raise ValueError(f"cams must be a [views,16] tensor (got {tuple(cams.shape) if torch.is_tensor(cams) else type(cams).__name__})")
+    if len(background) != 3:
+        raise ValueError("background must have 3 entries")
+    xyz, scale, f_dc, f_rest, cams = _f32(xyz), _f32(scale), _f32(f_dc), _f32(f_rest), _f32(cams)
+    n, views = xyz.shape[0], cams.shape[0]
+    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
+    if xyz.shape != (n, 3) or scale.shape != (n, 3) or f_dc.numel() != 3 * n or f_rest.numel() != 3 * n * (n_coef - 1):
+        raise ValueError("scene arrays disagree about the number of Gaussians")
+    _need_gpu(xyz, scale, f_dc, f_rest, cams, workspace)
+    lib = _lib.load()
+    dev = xyz.device
+    need = lib.sixdgs_splat_views_workspace_bytes(n, views, int(width), int(height))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    bg = torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
+    image = torch.empty(views, int(height), int(width), channels, dtype=torch.uint8, device=dev)
+    winner = torch.empty(views, int(height), int(width), dtype=torch.int32, device=dev) if want_winner else None
+    check(lib.sixdgs_splat_views(_p(xyz), _p(scale), int(scale_is_log), _p(f_dc), _p(f_rest if n_coef > 1 else None), int(sh_degree),
+                                 int(n_coef), n, _p(cams), views, int(width), int(height), int(channels), float(extent), float(near_z),
+                                 _p(bg), _p(image), _p(winner), _p(workspace), workspace.numel() * workspace.element_size(), _stream()),
+          "splat_views")
+    return (image, winner) if want_winner else image
+
+
 # ---------------------------------------------------------------------------------------------
 # scorer
 # ---------------------------------------------------------------------------------------------

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SIXDGS_ABI_VERSION 9   /* 9: sixdgs_score_backward_split / sixdgs_score_backward_split_workspace_bytes (the scorer backward split over ray groups); 8: sixdgs_score_backward / sixdgs_score_backward_workspace_bytes (backward of the scorer for training); 7: sixdgs_image_prep (uint8 -> resized, cropped, normalised planar fp32 in one pass); 6: sixdgs_tok_pack / sixdgs_tok_linear (dense products of the backbone stage on packed weight planes, with LayerNorm / GELU / residual fusion), sixdgs_tok_attention, sixdgs_im2col, sixdgs_u8_to_planar; the three-plane bf16 key format and its scorer kernel removed (sixdgs_split_planes, sixdgs_key_planes_bytes gone; key planes exist as scaled fp16 only); 5: sixdgs_scorer_weights carries the composite layer w4k / b4k / m4k (k_proj folded into ray-MLP layer 4 on the key-cache path), sixdgs_select_begin / _sample_stats take h_n_tok (token packing of the select sweep); 4: the select path's slack derived from |q| |k| (sixdgs_key_planes_norm_max; q + d_key_norm_max arguments) and its ray-sharded form (sample_stats / prepare / topk_u, d_uk, allow_fewer), tile maxima of U (u_tile_max); 3: sixdgs_score_select + sixdgs_select_* stages (top-k without materialised logits); 2: plane-format scorer entry points, pass1/pass2, grid kNN, split-K, distance target */
+#define SIXDGS_ABI_VERSION 10   /* 10: sixdgs_splat_views / sixdgs_splat_views_workspace_bytes (synthetic query views: the scene's Gaussians as z-buffered flat discs); 9: sixdgs_score_backward_split / sixdgs_score_backward_split_workspace_bytes (the scorer backward split over ray groups); 8: sixdgs_score_backward / sixdgs_score_backward_workspace_bytes (backward of the scorer for training); 7: sixdgs_image_prep (uint8 -> resized, cropped, normalised planar fp32 in one pass); 6: sixdgs_tok_pack / sixdgs_tok_linear (dense products of the backbone stage on packed weight planes, with LayerNorm / GELU / residual fusion), sixdgs_tok_attention, sixdgs_im2col, sixdgs_u8_to_planar; the three-plane bf16 key format and its scorer kernel removed (sixdgs_split_planes, sixdgs_key_planes_bytes gone; key planes exist as scaled fp16 only); 5: sixdgs_scorer_weights carries the composite layer w4k / b4k / m4k (k_proj folded into ray-MLP layer 4 on the key-cache path), sixdgs_select_begin / _sample_stats take h_n_tok (token packing of the select sweep); 4: the select path's slack derived from |q| |k| (sixdgs_key_planes_norm_max; q + d_key_norm_max arguments) and its ray-sharded form (sample_stats / prepare / topk_u, d_uk, allow_fewer), tile maxima of U (u_tile_max); 3: sixdgs_score_select + sixdgs_select_* stages (top-k without materialised logits); 2: plane-format scorer entry points, pass1/pass2, grid kNN, split-K, distance target */
 #define SIXDGS_E_BADARG (-1)
 #define SIXDGS_E_WORKSPACE (-2)
 #define SIXDGS_E_UNSUPPORTED (-3)
@@ -150,6 +150,33 @@ int sixdgs_emit_isocell(const float* xyz, const float* scale, int scale_is_log, 
 /* a10 alone: evaluate_viewdirs_color (sampling.py:116-124) for sh [R,3,ncoef] */
 int sixdgs_eval_sh_color(const float* sh, int n_coef, const float* dirs, int64_t r, int sh_degree, float* rgb,
                          sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Synthetic query views (ABI 10): the scene's Gaussians as flat, z-buffered discs.  A stand-in view
+ * generator whose images depend on the camera the way a real scene's do -- NOT the 3DGS rasteriser
+ * (no blending, no anisotropic footprint, no anti-aliasing, no gradients).  All arithmetic in fp32:
+ *  1. per view and Gaussian i: p = W xyz_i + t with [W | t] the view's w2c; skipped unless p.z > near_z;
+ *  2. u = fx p.x / p.z + cx, v = fy p.y / p.z + cy, r = max(extent * max(semi axes of i) * fx / p.z, 0.7072)
+ *     (the floor: every visible Gaussian covers at least the pixel its centre falls into);
+ *  3. i covers pixel (x, y) when (x + 0.5 - u)^2 + (y + 0.5 - v)^2 <= r^2; the whole disc has depth p.z;
+ *  4. a pixel's winner is the covering Gaussian of smallest p.z, equal p.z -> smaller index: the same
+ *     input gives the same bytes on every call;
+ *  5. colour of the winner: round(255 min(c, 1)) per channel, c = the emitters' SH colour (a10: + 0.5, clamped
+ *     at 0) for view direction normalize(xyz_i - camera centre) -- the colour of a ray that leaves
+ *     Gaussian i towards the camera.  Pixels without a winner get `background`; with channels == 4 alpha
+ *     is 255 on covered pixels and 0 elsewhere;
+ *  6. winner (may be NULL) receives the winning index, -1 where there is none.
+ * The scene arrays are the emitters' (scale [N,3], logs when scale_is_log != 0; f_dc [N,1,3], f_rest
+ * [N,n_coef-1,3]); cams and background are DEVICE arrays; n < 2^31, width, height <= 16384, views <= 65535,
+ * extent > 0, near_z >= 0.  Workspace: the 64-bit depth buffer and one packed colour per view and Gaussian. */
+size_t sixdgs_splat_views_workspace_bytes(int64_t n, int views, int width, int height);
+int sixdgs_splat_views(const float* xyz, const float* scale, int scale_is_log, const float* f_dc, const float* f_rest,
+                       int sh_degree, int n_coef, int64_t n,
+                       const float* cams /*[views][16]: w2c rows 0..2 (12 floats), fx, fy, cx, cy*/, int views, int width,
+                       int height, int channels /*3 or 4*/, float extent, float near_z,
+                       const float* background /*[3], in [0,1]*/, uint8_t* image /*[views][height][width][channels]*/,
+                       int32_t* winner /*[views][height][width] or NULL*/, void* ws, size_t ws_bytes,
+                       sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Scorer, scene side (once per scene): ray MLP + k_proj -> key cache
