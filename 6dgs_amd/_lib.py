@@ -103,6 +103,8 @@ SIGNATURES = {
     "sixdgs_distance_target_workspace_bytes": (sz, [i64]),
     "sixdgs_distance_target": (i32, [vp, vp, i64, vp, i32, vp, vp, vp, sz, vp]),
     "sixdgs_solve_pose": (i32, [vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "sixdgs_solve_pose_consensus_workspace_bytes": (sz, [i32, i32]),
+    "sixdgs_solve_pose_consensus": (i32, [vp, vp, i64, vp, vp, i32, vp, vp, i32, C.c_float, i32] + [vp] * 10 + [vp, sz, vp]),
 }
 
 _lib = None

@@ -1178,10 +1178,20 @@ def distance_target(rays_ori, rays_dir, pose, n_tokens: int, want_sum: bool = Fa
 # ---------------------------------------------------------------------------------------------
 # pose
 # ---------------------------------------------------------------------------------------------
+SOLVE_POSE_MAX_K = 256        # kMaxK of csrc/pose.hip
+CONSENSUS_MAX_K = 1024        # kConsMaxK of csrc/pose_consensus.hip
+POSE_PRIORS = {"uniform": 0, "score": 1}
+
+
 @_on_device
 def solve_pose(rays_ori, rays_dir, idx, val, up, gt_c2w=None):
     """Batched pose tail.  idx/val [B,k], up [B,3], gt_c2w [B,4,4] or None.
-    Returns dict(c2w[B,4,4], status[B], w_final[B,k], n_kept[B], centre[B,3], errors[B,2])."""
+    Returns dict(c2w[B,4,4], status[B], w_final[B,k], n_kept[B], centre[B,3], errors[B,2]).
+    k <= SOLVE_POSE_MAX_K (256: the kernel's per-image arrays); a longer top-k raises ValueError -- `solve_pose_consensus` takes up to 1024."""
+    if idx.dim() == 2 and idx.shape[1] > SOLVE_POSE_MAX_K:
+        k = idx.shape[1]
+        raise ValueError(f"6dgs_amd: solve_pose takes a top-k of at most {SOLVE_POSE_MAX_K} rays (got {k}); solve_pose_consensus takes up to "
+                         f"{CONSENSUS_MAX_K}")
     rays_ori, rays_dir, val, up = _f32(rays_ori), _f32(rays_dir), _f32(val), _f32(up)
     idx = _i64(idx)
     _need_gpu(rays_ori, rays_dir, idx, val, up)
@@ -1197,3 +1207,67 @@ def solve_pose(rays_ori, rays_dir, idx, val, up, gt_c2w=None):
     check(_lib.load().sixdgs_solve_pose(_p(rays_ori), _p(rays_dir), rays_ori.shape[0], _p(idx), _p(val), k, _p(up), _p(gt), b,
                                         _p(c2w), _p(status), _p(wf), _p(nk), _p(ctr), _p(err), _stream()), "solve_pose")
     return dict(c2w=c2w, status=status, w_final=wf, n_kept=nk, centre=ctr, errors=err)
+
+
+def _check_pose_operands(rays_ori, rays_dir, idx, val, up, gt_c2w):
+    """Shapes, dtypes and devices of the pose solvers' operands, before anything is marshalled: no wrong-sized tensor reaches a kernel."""
+    for name, t in (("rays_ori", rays_ori), ("rays_dir", rays_dir), ("idx", idx), ("val", val), ("up", up)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"6dgs_amd: {name} must be a tensor (got {type(t).__name__})")
+    if rays_ori.dim() != 2 or rays_ori.shape[1] != 3 or rays_dir.shape != rays_ori.shape:
+        raise ValueError(f"6dgs_amd: rays_ori and rays_dir must both be [R,3] (got {tuple(rays_ori.shape)} and {tuple(rays_dir.shape)})")
+    if idx.dim() != 2 or val.shape != idx.shape:
+        raise ValueError(f"6dgs_amd: idx and val must both be [B,k] (got {tuple(idx.shape)} and {tuple(val.shape)})")
+    if idx.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"6dgs_amd: idx must be an integer tensor (got {idx.dtype})")
+    for name, t in (("rays_ori", rays_ori), ("rays_dir", rays_dir), ("val", val), ("up", up)):
+        if not t.is_floating_point():
+            raise TypeError(f"6dgs_amd: {name} must be a floating-point tensor (got {t.dtype})")
+    b = idx.shape[0]
+    if tuple(up.shape) != (b, 3):
+        raise ValueError(f"6dgs_amd: up must be [B,3] = [{b},3] (got {tuple(up.shape)})")
+    if gt_c2w is not None:
+        if not torch.is_tensor(gt_c2w) or not gt_c2w.is_floating_point():
+            raise TypeError("6dgs_amd: gt_c2w must be a floating-point tensor or None")
+        if tuple(gt_c2w.shape) != (b, 4, 4):
+            raise ValueError(f"6dgs_amd: gt_c2w must be [B,4,4] = [{b},4,4] (got {tuple(gt_c2w.shape)})")
+
+
+@_on_device
+def solve_pose_consensus(rays_ori, rays_dir, idx, val, up, gt_c2w=None, *, inlier_scale, prior="uniform"):
+    """Batched consensus pose solver (include/sixdgs.h: sixdgs_solve_pose_consensus): every pair of the top-k rays proposes a camera
+    centre, all rays vote, the best supported proposal is refined and the pose assembled as by `solve_pose`.  Tolerates a top-k in
+    which most rays do not see the camera.  idx/val [B,k] with 2 <= k <= 1024, up [B,3], gt_c2w [B,4,4] or None; `inlier_scale`
+    (tau > 0, scene units) is the residual at which a ray's vote has fallen to one half; prior "uniform" or "score" (votes weighted
+    by val).  Returns the dict of `solve_pose` (status bit 3: no valid hypothesis, least-squares answer returned; n_kept = valid
+    rays) plus support [B] (soft inlier share at the final centre, in [0,1]), n_inliers [B] (int32), rms [B], winner [B,2] (int32)."""
+    _check_pose_operands(rays_ori, rays_dir, idx, val, up, gt_c2w)
+    if prior not in POSE_PRIORS:
+        raise ValueError(f"6dgs_amd: prior must be one of {sorted(POSE_PRIORS)} (got {prior!r})")
+    tau = float(inlier_scale)
+    if not (tau > 0.0 and tau < float("inf")):
+        raise ValueError(f"6dgs_amd: inlier_scale must be a positive finite number (got {inlier_scale})")
+    b, k = idx.shape
+    if not 2 <= k <= CONSENSUS_MAX_K:
+        raise ValueError(f"6dgs_amd: solve_pose_consensus takes a top-k of 2..{CONSENSUS_MAX_K} rays (got {k})")
+    rays_ori, rays_dir, val, up = _f32(rays_ori), _f32(rays_dir), _f32(val), _f32(up)
+    idx = _i64(idx)
+    gt = _f32(gt_c2w) if gt_c2w is not None else None
+    _need_gpu(rays_ori, rays_dir, idx, val, up, gt)
+    dev = idx.device
+    lib = _lib.load()
+    c2w = torch.empty(b, 4, 4, device=dev)
+    status = torch.empty(b, dtype=torch.int32, device=dev)
+    wf = torch.empty(b, k, device=dev)
+    nk = torch.empty(b, dtype=torch.int32, device=dev)
+    ctr = torch.empty(b, 3, device=dev)
+    err = torch.empty(b, 2, device=dev)
+    sup = torch.empty(b, device=dev)
+    nin = torch.empty(b, dtype=torch.int32, device=dev)
+    rms = torch.empty(b, device=dev)
+    win = torch.empty(b, 2, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(lib.sixdgs_solve_pose_consensus_workspace_bytes(b, k)), 256), dtype=torch.uint8, device=dev)
+    check(lib.sixdgs_solve_pose_consensus(_p(rays_ori), _p(rays_dir), rays_ori.shape[0], _p(idx), _p(val), k, _p(up), _p(gt), b, tau,
+                                          POSE_PRIORS[prior], _p(c2w), _p(status), _p(wf), _p(nk), _p(ctr), _p(err), _p(sup), _p(nin),
+                                          _p(rms), _p(win), _p(ws), ws.numel(), _stream()), "solve_pose_consensus")
+    return dict(c2w=c2w, status=status, w_final=wf, n_kept=nk, centre=ctr, errors=err, support=sup, n_inliers=nin, rms=rms, winner=win)

@@ -15,7 +15,8 @@ before writing the file.  Training, when no checkpoint exists, runs on rank 0 on
 
 Beyond the reference (keyword-only / extra flags, defaults reproduce it): --emitter / --max_ellipsoids / --rays_per_ellipsoid select
 full-scene emission (every Gaussian) instead of the reference's 1000-ellipsoid subsample; --skip_train evaluates random-init
-weights when no checkpoint exists (smoke runs); --n_iterations shortens training.
+weights when no checkpoint exists (smoke runs); --n_iterations shortens training; --pose_solver consensus (with --inlier_scale and
+--rays_to_output, up to 1024) solves the pose with the consensus solver (ops.solve_pose_consensus) instead of least squares.
 """
 from __future__ import annotations
 
@@ -61,6 +62,12 @@ def parse_args(argv=None):
                     help="split of the scorer's backward over the rays in the window (1 = unsplit, 0 = auto from the CU count)")
     ap.add_argument("--skip_train", action="store_true", help="never train: evaluate the checkpoint, or random-init weights when there is none")
     ap.add_argument("--batch_size", type=int, default=16, help="query images per scorer launch")
+    ap.add_argument("--pose_solver", choices=["ls", "consensus"], default="ls",
+                    help="ls = the reference's least-squares line intersection; consensus = hypothesise-and-verify over the top-k (tolerates outlier rays)")
+    ap.add_argument("--inlier_scale", type=float, default=None,
+                    help="consensus solver: inlier scale in scene units (default: 0.01 x the diagonal of the ray origins' bounding box)")
+    ap.add_argument("--rays_to_output", type=int, default=100,
+                    help="size of the top-k handed to the pose solver (100 = the reference; values above 1024 are capped at 1024; ls takes at most 256)")
     ap.add_argument("--arena_gb", type=float, default=0.0,
                     help="carve the big per-scene buffers (key planes, select workspace, chain workspace) from ONE device buffer of this many GB allocated once "
                          "(ops.Arena) instead of asking the allocator scene by scene: a sweep over scenes of growing size otherwise pays a 100-200 GB hipMalloc "
@@ -70,6 +77,15 @@ def parse_args(argv=None):
         ap.error("--data_parallel_train needs --batched_window")
     if args.backward_ray_groups < 0:
         ap.error("--backward_ray_groups must be >= 0 (0 = auto)")
+    if args.rays_to_output < 1:
+        ap.error("--rays_to_output must be >= 1")
+    args.rays_to_output = min(args.rays_to_output, 1024)
+    if args.inlier_scale is not None and not args.inlier_scale > 0:
+        ap.error("--inlier_scale must be > 0")
+    if args.pose_solver == "ls" and args.rays_to_output > 256:
+        ap.error("--pose_solver ls takes --rays_to_output <= 256; use --pose_solver consensus beyond")
+    if args.pose_solver == "consensus" and args.rays_to_output < 2:
+        ap.error("--pose_solver consensus needs --rays_to_output >= 2")
     return args, rest
 
 
@@ -88,7 +104,8 @@ def explore_model(model, **emission):
 def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[str, Any]", exp_dir_filepath: str, object_id: str, category_name: str,
                            starting_seed: int, lock_backbone: bool = True, device: str = "cuda", *, emission: Optional[dict] = None,
                            n_iterations: int = 1500, skip_train: bool = False, batch_size: int = 16, backbone: Optional[torch.nn.Module] = None,
-                           batched_window: bool = False, data_parallel_train: bool = False, backward_ray_groups: int = 1):
+                           batched_window: bool = False, data_parallel_train: bool = False, backward_ray_groups: int = 1,
+                           pose_solver: str = "ls", inlier_scale: Optional[float] = None, rays_to_output: int = 100):
     """pretrain_eval_attention.py:31-160 for one scene; returns the result dicts of the inference pass for ALL test views (rank 0;
     other ranks return their own block).
 
@@ -97,7 +114,10 @@ def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[s
     broadcast, seed, result gather) sit between the stages, where every rank is known to arrive.  Rank 0 trains a missing
     checkpoint inside a stage while the others wait in that stage's all-reduce (on the group with the long timeout: agree(long_wait=True),
     distributed.init_from_env).  data_parallel_train: every rank takes part in the training (train_id_module(data_parallel=True)), inside
-    the same stage; the ranks of a failing iteration leave it together."""
+    the same stage; the ranks of a failing iteration leave it together.
+
+    pose_solver / inlier_scale / rays_to_output: handed to both passes of test_pose_estimation."""
+    solver = dict(pose_solver=pose_solver, inlier_scale=inlier_scale, rays_to_output=rays_to_output)
     torch.manual_seed(starting_seed)
     print("data_path: ", checkpoint_args.source_path)
     emission = dict(EMISSION, **(emission or {}))
@@ -142,14 +162,14 @@ def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[s
         mine = scene_info.test_cameras[lo:hi]
         print("Testing overfit performances...")
         _, o_t, o_a, o_s, o_r = test_pose_estimation(mine, id_module, rays_ori, rays_dirs, rays_rgb, model_up, sequence_id=object_id,
-                                                     category_id=category_name, loss_fn=DistanceBasedScoreLoss(), batch_size=batch_size)
+                                                     category_id=category_name, loss_fn=DistanceBasedScoreLoss(), batch_size=batch_size, **solver)
         print("Overfit AVG translation error: ", o_t)
         print("Overfit AVG angular error: ", o_a)
         print("Overfit AVG score error: ", o_s)
         print("Overfit recall: ", o_r)
         print("Testing performances on same points...")
         results, t_t, t_a, t_s, t_r = test_pose_estimation(mine, id_module, rays_ori, rays_dirs, rays_rgb, model_up, sequence_id=object_id,
-                                                           category_id=category_name, save=False, save_all=False, batch_size=batch_size)
+                                                           category_id=category_name, save=False, save_all=False, batch_size=batch_size, **solver)
         for r in results:
             r["frame_id"] += lo                  # frame ids count the scene's test views, not the rank's block
         print("Test AVG translation error: ", t_t)
@@ -209,7 +229,8 @@ def main(argv=None, backbone: Optional[torch.nn.Module] = None) -> List[dict]:
                 emission=dict(emitter=args.emitter, max_ellipsoids=args.max_ellipsoids, rays_per_ellipsoid=args.rays_per_ellipsoid),
                 n_iterations=args.n_iterations, skip_train=args.skip_train, batch_size=args.batch_size, backbone=backbone,
                 batched_window=args.batched_window, data_parallel_train=args.data_parallel_train,
-                backward_ray_groups=args.backward_ray_groups)
+                backward_ray_groups=args.backward_ray_groups, pose_solver=args.pose_solver, inlier_scale=args.inlier_scale,
+                rays_to_output=args.rays_to_output)
             if rank == 0:
                 results.extend(obj)
         except RuntimeError:            # the only exception the reference survives per scene (pretrain_eval_attention.py:243-244)

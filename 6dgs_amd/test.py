@@ -21,6 +21,7 @@ import torch
 from . import ops
 
 _U8_TO_F32 = None
+POSE_SOLVERS = ("ls", "consensus")      # "ls": ops.solve_pose (the reference's least squares); "consensus": ops.solve_pose_consensus
 
 
 def _u8_lut(device):
@@ -173,10 +174,40 @@ def prime_image_graph(id_module, images) -> bool:
     return cache.run(id_module, images) is not None
 
 
+def default_inlier_scale(id_module, rays_ori) -> float:
+    """The consensus solver's inlier scale when none is given: 0.01 x the diagonal of the ray origins' bounding box.  Computed once per
+    ray tensor (one reduction and one D2H) and kept on the module, next to the key cache; not recomputed per batch.  Call it (or pass
+    `inlier_scale`) before capturing a graph: the D2H cannot be captured."""
+    held = id_module.__dict__.get("_inlier_scale_cache")
+    if held is not None and held[0].data_ptr() == rays_ori.data_ptr() and held[0].shape == rays_ori.shape and held[1] == rays_ori._version:
+        return held[2]
+    o = rays_ori.detach().reshape(-1, 3).float()
+    tau = 0.01 * float(torch.linalg.norm(o.amax(dim=0) - o.amin(dim=0)).item())
+    id_module.__dict__["_inlier_scale_cache"] = (rays_ori, rays_ori._version, tau)      # holds the tensor: its address cannot be reused meanwhile
+    return tau
+
+
+def _check_pose_solver(pose_solver, pose_prior):
+    if pose_solver not in POSE_SOLVERS:
+        raise ValueError(f"6dgs_amd: pose_solver must be one of {POSE_SOLVERS} (got {pose_solver!r})")
+    if pose_prior not in ops.POSE_PRIORS:
+        raise ValueError(f"6dgs_amd: pose_prior must be one of {sorted(ops.POSE_PRIORS)} (got {pose_prior!r})")
+
+
+def _solve(id_module, rays_ori, rays_dirs, idx, weights, up, gt_c2w, pose_solver="ls", inlier_scale=None, pose_prior="uniform"):
+    """The pose solve of a batch with the chosen solver; "ls" is the call this module always made."""
+    if pose_solver == "ls":
+        return ops.solve_pose(rays_ori, rays_dirs, idx, weights, up, gt_c2w)
+    _check_pose_solver(pose_solver, pose_prior)
+    tau = default_inlier_scale(id_module, rays_ori) if inlier_scale is None else float(inlier_scale)
+    return ops.solve_pose_consensus(rays_ori, rays_dirs, idx, weights, up, gt_c2w, inlier_scale=tau, prior=pose_prior)
+
+
 @torch.no_grad()
 def estimate_poses(id_module, images, rays_ori, rays_dirs, rays_rgb, gt_c2w=None, k: int = 100, workspace=None,
                    images_in_flight=None, profile=None, tokens=None, up=None, want_scores: bool = False, image_graph: bool = True,
-                   streamed_chunk_rays: Optional[int] = None, defer_status: bool = False):
+                   streamed_chunk_rays: Optional[int] = None, defer_status: bool = False, *, pose_solver: str = "ls",
+                   inlier_scale: Optional[float] = None, pose_prior: str = "uniform"):
     """One batch of the hot path: query images (uint8 [H,W,3|4] tensors on the GPU) -> poses.
     image prep -> backbone tokens + camera-up (PyTorch-ROCm) -> q_proj / scorer / top-k / pose solve (HIP).
     `tokens` / `up` inject the image-side boundary inputs instead.  Everything is enqueued on the current
@@ -185,7 +216,12 @@ def estimate_poses(id_module, images, rays_ori, rays_dirs, rays_rgb, gt_c2w=None
 
     defer_status: the select path's per-image status is not read inside (no sync in the middle of the batch: the whole call is
     one capturable stream of launches); the result then carries `packed` = [c2w (16) | select status] per image -- ONE D2H for
-    the caller -- and `resolve_poses(id_module, sol, packed_host)` re-does the images the select path refused (rare)."""
+    the caller -- and `resolve_poses(id_module, sol, packed_host)` re-does the images the select path refused (rare).
+
+    pose_solver: "ls" (default: ops.solve_pose, the reference's least squares, unchanged) or "consensus" (ops.solve_pose_consensus: tolerates
+    a top-k in which most rays do not see the camera; k up to 1024) with `inlier_scale` (None: default_inlier_scale) and `pose_prior`
+    ("uniform" or "score"); the returned dict then also carries support, n_inliers, rms and winner per image."""
+    _check_pose_solver(pose_solver, pose_prior)
     if tokens is None:
         res = None
         if image_graph and not torch.cuda.is_current_stream_capturing():
@@ -204,12 +240,14 @@ def estimate_poses(id_module, images, rays_ori, rays_dirs, rays_rgb, gt_c2w=None
         idx, weights, scores = id_module.score_tokens(tokens, rays_ori, rays_dirs, rays_rgb, k, want_scores=want_scores,
                                                       workspace=workspace, images_in_flight=images_in_flight, profile=profile,
                                                       defer_status=defer_status)
-    return _solve_batch(id_module, idx, weights, scores, tokens, up, rays_ori, rays_dirs, gt_c2w, defer_status)
+    return _solve_batch(id_module, idx, weights, scores, tokens, up, rays_ori, rays_dirs, gt_c2w, defer_status, pose_solver=pose_solver,
+                        inlier_scale=inlier_scale, pose_prior=pose_prior)
 
 
-def _solve_batch(id_module, idx, weights, scores, tokens, up, rays_ori, rays_dirs, gt_c2w, defer_status):
+def _solve_batch(id_module, idx, weights, scores, tokens, up, rays_ori, rays_dirs, gt_c2w, defer_status, *, pose_solver: str = "ls",
+                 inlier_scale: Optional[float] = None, pose_prior: str = "uniform"):
     """The end of a batch: pose solve on the selected rays; with defer_status the select statuses ride along with the poses (`packed`)."""
-    sol = ops.solve_pose(rays_ori, rays_dirs, idx, weights, up, gt_c2w)
+    sol = _solve(id_module, rays_ori, rays_dirs, idx, weights, up, gt_c2w, pose_solver, inlier_scale, pose_prior)
     sol.update(idx=idx, weights=weights, scores=scores, tokens=tokens, up=up)
     if defer_status:
         pend = getattr(id_module, "pending_select", None)
@@ -217,13 +255,16 @@ def _solve_batch(id_module, idx, weights, scores, tokens, up, rays_ori, rays_dir
         sol["packed"] = torch.cat([sol["c2w"].reshape(-1, 16), st[:, None]], dim=1)
         sol["pending_select"] = pend
         sol["_inputs"] = (rays_ori, rays_dirs, gt_c2w)
+        sol["_solver"] = (pose_solver, inlier_scale, pose_prior)
     return sol
 
 
 @torch.no_grad()
-def resolve_poses(id_module, sol, packed_host):
+def resolve_poses(id_module, sol, packed_host, *, pose_solver: Optional[str] = None, inlier_scale: Optional[float] = None,
+                  pose_prior: Optional[str] = None):
     """After the one D2H of a defer_status batch: c2w [B,4,4] on the host; images whose select status is negative (the bounds could
-    not decide them) are scored by the two-pass scorer and solved again -- eagerly, outside any graph."""
+    not decide them) are scored by the two-pass scorer and solved again -- eagerly, outside any graph -- by the solver the batch was
+    solved with (recorded in `sol`; pose_solver / inlier_scale / pose_prior override it)."""
     c2w = packed_host[:, :16].reshape(-1, 4, 4).clone()
     pend = sol.get("pending_select")
     if pend is None:
@@ -235,7 +276,9 @@ def resolve_poses(id_module, sol, packed_host):
     idx, weights = sol["idx"].clone(), sol["weights"].clone()
     idx, weights, redo = id_module.finish_select(idx, weights, pend, status_host=status)
     rays_ori, rays_dirs, gt = sol["_inputs"]
-    again = ops.solve_pose(rays_ori, rays_dirs, idx, weights, sol["up"], gt)
+    rec = sol.get("_solver", ("ls", None, "uniform"))
+    again = _solve(id_module, rays_ori, rays_dirs, idx, weights, sol["up"], gt, rec[0] if pose_solver is None else pose_solver,
+                   rec[1] if inlier_scale is None else inlier_scale, rec[2] if pose_prior is None else pose_prior)
     sol.update(again, idx=idx, weights=weights)
     return again["c2w"].cpu()
 
@@ -262,8 +305,13 @@ class PoseStream:
     submit waits for the caller's stream, so a PoseStream may follow `estimate_poses` calls on the same module; do not call `estimate_poses(image_graph=True)`
     BETWEEN the submits of a PoseStream without a host sync in between -- its replay would rewrite buffers the other stream may still read."""
 
-    def __init__(self, id_module, rays_ori, rays_dirs, rays_rgb, k: int = 100, workspace=None, images_in_flight=None):
+    def __init__(self, id_module, rays_ori, rays_dirs, rays_rgb, k: int = 100, workspace=None, images_in_flight=None, *, pose_solver: str = "ls",
+                 inlier_scale: Optional[float] = None, pose_prior: str = "uniform"):
+        _check_pose_solver(pose_solver, pose_prior)
         self.idm, self.rays, self.k = id_module, (rays_ori, rays_dirs, rays_rgb), k
+        if pose_solver == "consensus" and inlier_scale is None:
+            inlier_scale = default_inlier_scale(id_module, rays_ori)        # once per stream, not per batch
+        self.solver = dict(pose_solver=pose_solver, inlier_scale=inlier_scale, pose_prior=pose_prior)
         self.workspace, self.images_in_flight = workspace, images_in_flight
         self.image_stream = torch.cuda.Stream(device=rays_ori.device)      # (a high-priority image stream was measured in round 6: no difference, profiles/r06_pipeline_ab.md)
         self._fence = None            # recorded on the caller's stream at the START of the previous submit
@@ -309,7 +357,7 @@ class PoseStream:
                                                      images_in_flight=self.images_in_flight, profile=profile, defer_status=True)
         if up_ready is not None:
             main.wait_event(up_ready)
-        sol = _solve_batch(self.idm, idx, weights, scores, tokens, up, self.rays[0], self.rays[1], gt_c2w, True)
+        sol = _solve_batch(self.idm, idx, weights, scores, tokens, up, self.rays[0], self.rays[1], gt_c2w, True, **self.solver)
         # the batch's ONE D2H, behind an event instead of a device sync: [c2w (16) | select status | solve status | t err | ang err | mean kept weight | kept]
         full = torch.cat([sol["packed"], sol["status"].to(torch.float32)[:, None], sol["errors"].to(torch.float32),
                           (sol["w_final"].sum(dim=1) / sol["n_kept"].clamp(min=1))[:, None], sol["n_kept"].to(torch.float32)[:, None]], dim=1)
@@ -395,13 +443,21 @@ def test_pose_estimation(
     token_override: Optional[List[torch.Tensor]] = None,
     up_override: Optional[torch.Tensor] = None,
     save_dir: Optional[str] = None,
+    pose_solver: str = "ls",
+    inlier_scale: Optional[float] = None,
+    pose_prior: str = "uniform",
+    rays_to_output: int = 100,
 ):
     """See module docstring.  `token_override` / `up_override` inject the boundary's image-side inputs
     (tokens [T,398] per image, camera-up [B,3]) -- used by the parity fixtures, where DINOv2 is absent.
 
     `save` / `save_all` (test.py:94-106,137-140,164-166,202-214): the per-image dump of everything the estimate was made from
     (`sample_results_<img_idx>.th`, image 0 only unless `save_all`), same keys as the reference.  The reference writes into a
-    developer's home directory; here the directory is `save_dir`, else $SIXDGS_SAVE_DIR, else ./sample_results."""
+    developer's home directory; here the directory is `save_dir`, else $SIXDGS_SAVE_DIR, else ./sample_results.
+
+    `pose_solver` / `inlier_scale` / `pose_prior`: as in estimate_poses ("ls", the default, is the reference's solver; the results schema is the
+    same with "consensus").  `rays_to_output`: the size of the top-k (100 = the reference; "ls" takes at most 256, "consensus" 1024)."""
+    _check_pose_solver(pose_solver, pose_prior)
     if save:
         save_dir = save_dir or os.environ.get("SIXDGS_SAVE_DIR") or os.path.join(os.getcwd(), "sample_results")
         os.makedirs(save_dir, exist_ok=True)
@@ -412,7 +468,14 @@ def test_pose_estimation(
     model_up = torch.divide(model_up, torch.linalg.norm(model_up, dim=-1, keepdim=True))  # test.py:40 (unused afterwards)
     n = len(cameras_info)
     translation_errors, angular_errors, recalls, avg_loss_scores, results = [], [], [], [], []
-    k = 100
+    k = ops.check_topk(rays_to_output)
+    if pose_solver == "ls" and k > ops.SOLVE_POSE_MAX_K:
+        raise ValueError(f"6dgs_amd: pose_solver='ls' takes rays_to_output <= {ops.SOLVE_POSE_MAX_K} (got {k}); pose_solver='consensus' takes up to "
+                         f"{ops.CONSENSUS_MAX_K}")
+    if pose_solver == "consensus" and k < 2:
+        raise ValueError("6dgs_amd: pose_solver='consensus' needs rays_to_output >= 2")
+    if pose_solver == "consensus" and inlier_scale is None and n > 0:
+        inlier_scale = default_inlier_scale(id_module, rays_ori)
     start_time = time.time()
     # batches of EQUAL size (19 views at batch_size 16: 10 + 9, not 16 + 3): the reference scores one image at a time, so the cut is free, and a short last
     # batch runs the sweep at the efficiency of a near-empty launch (one or two tiles pull every key tile from HBM for themselves)
@@ -448,7 +511,7 @@ def test_pose_estimation(
     streamable = (loss_fn is None and not save and os.environ.get("SIXDGS_NO_PIPELINE") != "1" and
                   (token_override is not None or all(np.asarray(c.image).dtype == np.uint8 for c in cameras_info)))
     if streamable and n > 0:
-        ps = PoseStream(id_module, rays_ori, rays_dirs, rays_rgb, k)
+        ps = PoseStream(id_module, rays_ori, rays_dirs, rays_rgb, k, pose_solver=pose_solver, inlier_scale=inlier_scale, pose_prior=pose_prior)
         pending = None
         for b0 in list(range(0, n, batch_size)) + [None]:
             cur = None
@@ -529,7 +592,7 @@ def test_pose_estimation(
                 if saving[i]:   # test.py:137-140
                     dumps[i].update(all_target_weights=target_scores.cpu(), loss=avg_score[i], recall=recall[i])
             idx, weights = torch.stack(new_idx), torch.stack(new_w)
-        sol = ops.solve_pose(rays_ori, rays_dirs, idx, weights, up, gt)
+        sol = _solve(id_module, rays_ori, rays_dirs, idx, weights, up, gt, pose_solver, inlier_scale, pose_prior)
         c2w = sol["c2w"].cpu()
         status = sol["status"].cpu()
         err = sol["errors"].cpu()

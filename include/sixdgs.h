@@ -478,6 +478,50 @@ int sixdgs_solve_pose(const float* rays_ori, const float* rays_dir, int64_t r, c
                       int batch, float* c2w, int32_t* status, float* w_final, int32_t* n_kept, float* centre /*[B,3]*/,
                       float* errors, sixdgs_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Consensus pose solver (added under ABI 10, additive: nothing above changes signature or meaning).  A hypothesise-and-verify
+ * estimator of the camera centre over the same top-k, for top-k lists in which many rays do not see the camera; the pose is
+ * then assembled as by sixdgs_solve_pose.  Deterministic, no random numbers.  All arithmetic in fp32.
+ *
+ * Per image b.  A POSITION is an entry 0..k-1 of idx[b,:]; it is VALID when 0 <= idx < r (other entries are padding: they
+ * neither vote nor form hypotheses); n = number of valid positions.  o_i, d_i: origin and (unit) direction of the ray at
+ * position i.  There is no duplicate-origin filter.  Prior p_i: prior = 0: 1/n; prior = 1: v_i / sum v with v_i = val[b,i]
+ * where that is > 0, else 0.  tau > 0: inlier scale in scene units.
+ *   r_i(c)     distance of c to the line (o_i, d_i): |v - (v.d_i) d_i| with v = c - o_i;    front_i(c) = [(c - o_i).d_i > 0].
+ *  1. Hypotheses: pairs of positions (i, j).  k <= 256: every pair i < j.  k > 256: (i, (i + m) mod k), m = 1..floor(32768 / k)
+ *     (the top-k is sorted by score: each ray meets its neighbours in rank).  With w0 = o_i - o_j, b = d_i.d_j, d = d_i.w0,
+ *     e = d_j.w0, den = 1 - b^2, s = (b e - d) / den, t = (e - b d) / den the candidate is the midpoint of the closest approach,
+ *     c = ((o_i + s d_i) + (o_j + t d_j)) / 2.  A pair is INVALID when a position of it is padding, den <= 1e-6, s <= 0 or t <= 0
+ *     (the camera is in front of both rays).
+ *  2. Support S(c) = sum_i p_i front_i(c) / (1 + (r_i(c) / tau)^2), in [0, 1], summed in position order.  The winner is the valid
+ *     hypothesis of largest S; equal S: the smallest (i, j) in lexicographic order, (i, j) as listed in 1.  (The sweep evaluates S
+ *     with the prior left un-normalised and a hardware reciprocal -- neither changes the order beyond fp32 rounding; hypotheses
+ *     whose supports differ by less than that are the same basin, and the refinement below takes them to the same centre.)
+ *  3. Refinement from the winner's c, 8 iterations, tau fixed: w_i = p_i front_i(c) / (1 + (r_i(c) / tau)^2)^2,
+ *     c <- solve(sum w_i (I - d_i d_i^T), sum w_i (I - d_i d_i^T) o_i) (LU with partial pivoting).  A determinant that is not
+ *     positive or < 1e-7 (sum w_i)^3, or a non-finite solution, ends the refinement at the last good c.  SUMS over the rays
+ *     (here and below) run on a fixed tree: positions in groups of 64 consecutive ones; inside a group the butterfly
+ *     x_l += x_(l xor s), s = 32, 16, .. 1; the group sums added in group order.
+ *  4. Tail as in sixdgs_solve_pose: final w_i at the final c, written to w_final renormalised to sum 1 (0 for padding); watch =
+ *     normalised sum w_i d_i; make_rotation_mat(-watch, up[b]); singular -> I; c2w = [inv(R) | c]; NaN -> I4; errors against
+ *     gt_c2w when given.
+ *  5. No valid hypothesis (or n < 2): status bit 3; c = the plain unweighted least-squares centre over the valid rays (NaN when
+ *     its determinant < 1e-7, bit 2), w_i = p_i front_i(c), then the tail of 4; winner = (-1, -1).
+ * outputs: those of sixdgs_solve_pose (status bits 0..2 as there, bit 3 = no hypothesis; n_kept = n), and -- each may be NULL --
+ *   support [B]     S at the final centre (normalised prior): a confidence in [0, 1];
+ *   n_inliers [B]   rays with front_i and r_i <= 2 tau at the final centre;
+ *   rms [B]         sqrt(sum w_i r_i^2 / sum w_i) with the final w_i;
+ *   winner [B,2]    the winning pair's positions.
+ * Workspace: the best (S, pair) of every block of 256 hypotheses, per image.  SIXDGS_E_BADARG for k < 2, k > 1024, tau <= 0 (or
+ * tau^2 not a finite non-zero fp32 number), prior outside {0, 1}, batch > 65535 or ws_bytes below the query -- answered without
+ * touching the GPU.  Two kernels on `stream`, no sync, capturable. */
+size_t sixdgs_solve_pose_consensus_workspace_bytes(int batch, int k);
+int sixdgs_solve_pose_consensus(const float* rays_ori, const float* rays_dir, int64_t r, const int64_t* idx /*[B,k]*/,
+                                const float* val /*[B,k]*/, int k, const float* up /*[B,3]*/, const float* gt_c2w /*[B,4,4] or NULL*/,
+                                int batch, float tau, int prior, float* c2w, int32_t* status, float* w_final, int32_t* n_kept,
+                                float* centre /*[B,3]*/, float* errors, float* support, int32_t* n_inliers, float* rms,
+                                int32_t* winner, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

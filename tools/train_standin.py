@@ -8,7 +8,11 @@ errors of test_pose_estimation with the initial weights, trains with train_id_mo
 and candidate counts, select / two-pass / CPU checker agreement (top-100 under the tie policy of tests/test_gpu_configs.py, scores,
 pose), how peaked the softmax became, and the time of render_views at 500 k Gaussians / 800 x 800.  Everything goes to the output
 file together with the command line; a number that was not measured is not written.  tests/test_gpu_trained_scorer.py uses the
-functions below for a shorter run."""
+functions below for a shorter run.
+
+--pose-solver both: on the trained weights, additionally, least squares (k = 100) against the consensus solver (k = 100, 256, 1024) on the
+training and the held-out views -- median errors, the distribution of `support` and `n_inliers`, and both solvers' GPU time per batch of 8
+images from HIP events -- written to --consensus-out (profiles/pose_consensus.md)."""
 import argparse
 import functools
 import importlib
@@ -184,6 +188,104 @@ def time_render(n_gauss: int = 500_000, size: int = 800, views: int = 4, repeats
     return float(np.median(times)), float(min(times)), float(max(times))
 
 
+CONSENSUS_KS = (100, 256, 1024)
+
+
+@torch.no_grad()
+def solver_comparison(idm, cams, rays, batch: int = 8):
+    """Per view of `cams`: least squares at k = 100 and consensus at CONSENSUS_KS on the module's current weights, one scorer pass per k.
+    -> {(solver, k): dict(t=[..], r=[..], bad=[..], support=[..], n_inliers=[..])}, errors as the solvers report them against the view's pose."""
+    _, _, ops, T = modules()
+    o, d, c = rays
+    tau = T.default_inlier_scale(idm, o)
+    out = {}
+    for b0 in range(0, len(cams), batch):
+        part = cams[b0:b0 + batch]
+        toks, up = image_side(idm, part)
+        gt = torch.stack([T.gt_pose_and_intrinsics(cam, "cpu")[0] for cam in part]).cuda()
+        for k in CONSENSUS_KS:
+            idx, val, _ = idm.score_tokens(toks, o, d, c, k, want_scores=False)
+            sols = [("consensus", ops.solve_pose_consensus(o, d, idx, val, up, gt, inlier_scale=tau))]
+            if k == 100:
+                sols.append(("ls", ops.solve_pose(o, d, idx, val, up, gt)))
+            for name, sol in sols:
+                row = out.setdefault((name, k), dict(t=[], r=[], bad=[], support=[], n_inliers=[]))
+                st = sol["status"].cpu().numpy()
+                err = sol["errors"].cpu().numpy().astype(np.float64)
+                row["bad"] += ((st & 6) != 0).tolist()
+                row["t"] += np.where((st & 6) != 0, np.nan, err[:, 0]).tolist()
+                row["r"] += np.where((st & 6) != 0, np.nan, err[:, 1]).tolist()
+                if name == "consensus":
+                    row["support"] += sol["support"].cpu().tolist()
+                    row["n_inliers"] += sol["n_inliers"].cpu().tolist()
+    return out, tau
+
+
+@torch.no_grad()
+def time_solvers(idm, cams, rays, repeats: int = 20):
+    """GPU time of one solver call on a batch of 8 images (HIP events around the call: both kernels of the consensus solver, the one of least
+    squares), median / min / max over `repeats` calls after a warm-up.  -> {(solver, k): (median, min, max) in microseconds}."""
+    _, _, ops, T = modules()
+    o, d, c = rays
+    tau = T.default_inlier_scale(idm, o)
+    toks, up = image_side(idm, cams[:8])
+    out = {}
+    for k in CONSENSUS_KS:
+        idx, val, _ = idm.score_tokens(toks, o, d, c, k, want_scores=False)
+        calls = [("consensus", lambda: ops.solve_pose_consensus(o, d, idx, val, up, inlier_scale=tau))]
+        if k <= ops.SOLVE_POSE_MAX_K:
+            calls.append(("ls", lambda: ops.solve_pose(o, d, idx, val, up)))
+        for name, fn in calls:
+            fn()
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(repeats):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                times.append(a.elapsed_time(b) * 1e3)
+            out[(name, k)] = (float(np.median(times)), float(min(times)), float(max(times)))
+    return out
+
+
+def _quantiles(a):
+    a = np.asarray(a, np.float64)
+    return "min {:.3g}, quartiles {:.3g} / {:.3g} / {:.3g}, max {:.3g}".format(a.min(), *np.percentile(a, [25, 50, 75]), a.max())
+
+
+def consensus_report(args, cmd, comparison, tau, timing, rays_n, extra=None):
+    L = ["# Consensus pose solver: measurements", "",
+         f"Command: `{cmd}`", "",
+         f"Scene, views, training and emission as in `profiles/trained_standin.md` (`make_scene({args.gaussians}, {args.seed})`, {args.train_views} training and "
+         f"{args.held_views} held-out rendered views, {args.iterations} iterations; {rays_n} rays).  Inlier scale: the default, 0.01 x the diagonal of the ray "
+         f"origins' bounding box = {tau:.4g} scene units; uniform prior.", "",
+         "## Least squares against consensus on the trained stand-in weights", "",
+         "Errors as the solvers report them against each view's pose (translation = camera centre, scene units; rotation in degrees); median over the views; "
+         "a view whose pose came back NaN / identity counts as unusable and is left out of the medians.", "",
+         "| views | solver | k | translation | rotation | unusable |", "|---|---|---|---|---|---|"]
+    for split in ("train", "held"):
+        for key in [("ls", 100)] + [("consensus", k) for k in CONSENSUS_KS]:
+            row = comparison[split][key]
+            L.append(f"| {split} ({len(row['t'])}) | {'least squares' if key[0] == 'ls' else 'consensus'} | {key[1]} | {_med(row['t']):.4f} | {_med(row['r']):.2f} | {int(np.sum(row['bad']))} |")
+    L += ["", "Distribution of the consensus solver's confidence outputs over the views:", ""]
+    for split in ("train", "held"):
+        for k in CONSENSUS_KS:
+            row = comparison[split][("consensus", k)]
+            L.append(f"* {split}, k = {k}: `support` {_quantiles(row['support'])}; `n_inliers` {_quantiles(row['n_inliers'])}")
+    L += ["", "## Solver time per batch of 8 images", "",
+          "HIP events around one call (`k_consensus_sweep` + `k_consensus_finish`; `k_solve_pose` for least squares), same process, same box, median (min - max) of 20 calls:", "",
+          "| solver | k | microseconds |", "|---|---|---|"]
+    for key in sorted(timing, key=lambda x: (x[1], x[0])):
+        med, lo, hi = timing[key]
+        L.append(f"| {'least squares' if key[0] == 'ls' else 'consensus'} | {key[1]} | {med:.0f} ({lo:.0f} - {hi:.0f}) |")
+    if extra:
+        L += ["", extra.rstrip()]
+    L.append("")
+    return "\n".join(L)
+
+
 def _med(a):
     a = np.asarray(a, np.float64)
     return float(np.nanmedian(a)) if np.isfinite(a).any() else float("nan")
@@ -253,6 +355,10 @@ def main():
     ap.add_argument("--test-durations", default=None, help="a line on the measured duration of the new GPU tests, copied into the report")
     ap.add_argument("--ckpt", default="id_module.th", help="where the trained checkpoint is written (default: the current directory)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trained_standin.md"))
+    ap.add_argument("--pose-solver", choices=["ls", "both"], default="ls",
+                    help="both: also compare least squares with the consensus solver on the trained weights and time them (see --consensus-out)")
+    ap.add_argument("--consensus-out", default=os.path.join(ROOT, "profiles", "pose_consensus.md"))
+    ap.add_argument("--consensus-extra", default=None, help="a markdown file appended to the consensus report (figures collected elsewhere)")
     args = ap.parse_args()
     from oracle import oracle as checker
     checker.build()
@@ -272,6 +378,17 @@ def main():
     seconds = {"train": time.time() - t0}
     errs["train"]["after"], errs["held"]["after"] = pose_errors(idm, train_cams, rays, up), pose_errors(idm, held_cams, rays, up)
     parity = trained_parity(idm, held_cams, rays, checker)
+    if args.pose_solver == "both":
+        comparison = {}
+        comparison["train"], tau = solver_comparison(idm, list(train_cams), rays)
+        comparison["held"], _ = solver_comparison(idm, list(held_cams), rays)
+        timing = time_solvers(idm, list(held_cams), rays)
+        extra = open(args.consensus_extra).read() if args.consensus_extra else None
+        ctext = consensus_report(args, "python tools/train_standin.py " + " ".join(sys.argv[1:]), comparison, tau, timing, errs["rays"], extra)
+        os.makedirs(os.path.dirname(os.path.abspath(args.consensus_out)), exist_ok=True)
+        with open(args.consensus_out, "w") as f:
+            f.write(ctext)
+        print(ctext)
     render_ms = None if args.no_render_timing else time_render()
     text = report(args, "python tools/train_standin.py " + " ".join(sys.argv[1:]), loss, errs, parity, render_ms, seconds, args.test_durations)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
