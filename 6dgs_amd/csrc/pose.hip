@@ -1,4 +1,4 @@
-// pose.hip -- per-image pose assembly from the top-k rays (one workgroup of four wavefronts per image: the per-ray parts in parallel, every sum in index order on one lane):
+// pose.hip -- per-image pose assembly from the top-k rays (one workgroup of 1024 threads per image: the per-ray parts in parallel, every sum in index order on one lane):
 // duplicate-origin filter, least-squares line intersection, exclude_negatives reweighting, viewing
 // direction, rotation assembly, NaN / singular fall-backs, pose errors.
 // replaces pose_estimation/test.py:157-198,216-218,268-288 with line_intersection.py:5-34,75-154 and
@@ -59,27 +59,43 @@ __global__ void __launch_bounds__(kPoseThreads) k_solve_pose(PoseArgs A) {
   const int64_t* idx = A.idx + (int64_t)b * k;
 
   POSE_T(0)
-  // ---- gather the selected rays (negative / out-of-range indices = padding of a short top-k) -------
+  // ---- gather the selected rays (negative / out-of-range indices = padding, at any position): the valid ones compacted in index order -------
+  int vpos = -1, kv = 0;    // vpos: the compact position of entry tid among the valid entries, or -1 (k <= kMaxK <= kPoseThreads); kv: their count
   {
-    const int i = tid;      // k <= kMaxK <= kPoseThreads
+    const int i = tid;
     bool ok = false;
+    float o[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f}, w = 0.f;
     if (i < k) {
       const int64_t id = idx[i];
       ok = id >= 0 && id < A.r;
-      for (int c = 0; c < 3; ++c) {
-        so[3 * i + c] = ok ? A.rays_ori[3 * id + c] : NAN;
-        sd[3 * i + c] = ok ? A.rays_dir[3 * id + c] : NAN;
+      if (ok) {
+        for (int c = 0; c < 3; ++c) {
+          o[c] = A.rays_ori[3 * id + c];
+          d[c] = A.rays_dir[3 * id + c];
+        }
+        w = A.val[(int64_t)b * k + i];
       }
-      sw[i] = ok ? A.val[(int64_t)b * k + i] : 0.f;
       cnt[i] = 0;
     }
     for (int p = tid; p < 3 * k; p += kPoseThreads) anyf[p] = 0;
-    const int nv = __popcll(__ballot(ok));                          // padding entries sit at the tail (sorted top-k): the valid ones are a prefix
-    if (lane == 0) s_valid[tid >> 6] = nv;
+    const unsigned long long mv = __ballot(ok);
+    if (lane == 0) s_valid[tid >> 6] = __popcll(mv);
+    __syncthreads();
+    int before = 0;                                                 // valid entries in the waves before this one
+    for (int w2 = 0; w2 < kPoseThreads / 64; ++w2) {
+      if (w2 < (tid >> 6)) before += s_valid[w2];
+      kv += s_valid[w2];
+    }
+    if (ok) {
+      vpos = before + __popcll(mv & ((1ull << lane) - 1ull));
+      for (int c = 0; c < 3; ++c) {
+        so[3 * vpos + c] = o[c];
+        sd[3 * vpos + c] = d[c];
+      }
+      sw[vpos] = w;
+    }
   }
   __syncthreads();
-  int kv = 0;
-  for (int w = 0; w < kPoseThreads / 64; ++w) kv += s_valid[w];
   POSE_T(1)
 
   // ---- a17: torch.unique(rows, counts) + isin(assume_unique=True).any(dim=1)  (test.py:157-162) ------
@@ -208,8 +224,7 @@ __global__ void __launch_bounds__(kPoseThreads) k_solve_pose(PoseArgs A) {
     term[12 * i + 2] = cd[3 * i + 2] * w1;
   }
   __syncthreads();
-  if (A.w_final)
-    for (int i = tid; i < k; i += kPoseThreads) A.w_final[(int64_t)b * k + i] = (i < kv && keep[i]) ? cw[cpos[i]] : 0.f;
+  if (A.w_final && tid < k) A.w_final[(int64_t)b * k + tid] = (vpos >= 0 && keep[vpos]) ? cw[cpos[vpos]] : 0.f;   // back at the original position
   if (tid != 0) return;
   float wd[3] = {0.f, 0.f, 0.f};
   for (int i = 0; i < m; ++i) {

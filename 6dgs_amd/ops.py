@@ -1187,7 +1187,8 @@ POSE_PRIORS = {"uniform": 0, "score": 1}
 def solve_pose(rays_ori, rays_dir, idx, val, up, gt_c2w=None):
     """Batched pose tail.  idx/val [B,k], up [B,3], gt_c2w [B,4,4] or None.
     Returns dict(c2w[B,4,4], status[B], w_final[B,k], n_kept[B], centre[B,3], errors[B,2]).
-    k <= SOLVE_POSE_MAX_K (256: the kernel's per-image arrays); a longer top-k raises ValueError -- `solve_pose_consensus` takes up to 1024."""
+    k <= SOLVE_POSE_MAX_K (256: the kernel's per-image arrays); a longer top-k raises ValueError -- `solve_pose_consensus` takes up to 1024.
+    Entries with idx < 0 or idx >= R are padding at any position: they are skipped, and w_final is 0 there."""
     if idx.dim() == 2 and idx.shape[1] > SOLVE_POSE_MAX_K:
         k = idx.shape[1]
         raise ValueError(f"6dgs_amd: solve_pose takes a top-k of at most {SOLVE_POSE_MAX_K} rays (got {k}); solve_pose_consensus takes up to "

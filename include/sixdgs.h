@@ -470,8 +470,11 @@ int sixdgs_distance_target(const float* rays_ori, const float* rays_dir, int64_t
 /* For each image b: duplicate-origin filter, unweighted LS centre (NaN when det < 1e-7),
  * exclude_negatives reweighting, watch direction, make_rotation_mat(-watch, up[b]), singular -> I,
  * c2w = [inv(R) | centre], NaN -> I4.
+ * A POSITION is an entry 0..k-1 of idx[b,:]; it is VALID when 0 <= idx < r (other entries are padding, at any position: they
+ * neither filter nor solve, and val is not read there).  The valid positions are taken in index order: a padded list gives the
+ * bits of the call on the list without its padding.  No valid position: identity, status bits 1 and 2, n_kept 0.  1 <= k <= 256.
  * outputs: c2w [B,4,4]; status [B] bit0 = singular rotation, bit1 = NaN pose (identity returned),
- * bit2 = NaN centre; w_final [B,k] (0 for filtered rays), n_kept [B]; errors [B,2] =
+ * bit2 = NaN centre; w_final [B,k] (0 for filtered rays and for padding), n_kept [B]; errors [B,2] =
  * (translation error, angular error in degrees) against gt_c2w when gt_c2w != NULL. */
 int sixdgs_solve_pose(const float* rays_ori, const float* rays_dir, int64_t r, const int64_t* idx /*[B,k]*/,
                       const float* val /*[B,k]*/, int k, const float* up /*[B,3]*/, const float* gt_c2w /*[B,4,4]*/,
