@@ -235,6 +235,106 @@ constexpr int kLdsX = kKBaseX + 6 * kQStageX;   // 160 KiB
 // MFMA shape of the tile's matrix work.  Same cycles per FLOP; the chip holds a higher clock on the 16x16x32 form (profiles/sweep_mfma_16x16x32.md).
 constexpr int kMfma32 = 0;     // v_mfma_f32_32x32x16_f16: a wave's 64 tokens x 128 rays are 2 x 4 blocks, a 32-k slab is two k-steps
 constexpr int kMfma16 = 1;     // v_mfma_f32_16x16x32_f16: 4 x 8 blocks, a slab is ONE k-step (the select sweep only; lane maps: sweep_layout.h)
+constexpr int kMfma16Tile = 2; // the same tile with the whole epilogue behind the tile's last slab (SIXDGS_SWEEP_EPILOGUE=tile: the A/B of the block-wise epilogue)
+
+// ---- The block-wise epilogue of the kMfma16 tile (k_logits_f16x<.., kMfma16>).  The 16 accumulators of ray block rb are final after step rb of
+// slab 11 and are not written again before step rb of the next tile's slab 0, whose first MFMA per token block starts from the inline constant 0:
+// the epilogue of a tile runs on them where they lie, in halves k = 2 rb + h (h: registers 2 h, 2 h + 1 of the block's 4 token blocks), one half
+// per step g = k of the 16 steps g = 0..15 of slab 11 and the next slab 0 (steps 1 and 14 take both halves of blocks 0 and 7).  Blocks 4..7 are
+// thus carried into the next tile or, behind the last tile of a group, drained after the tile loop.  Per value the same operations in the same
+// order as the per-tile epilogue (kMfma16Tile): the same bits.
+typedef float sweep_f32x4 __attribute__((ext_vector_type(4)));
+struct SweepEpi {
+  float cfl_next, cfl;      // exp2 scale of the tile under the MFMAs / of the tile whose epilogue is under way (taken over at slab 11)
+  int lim;                  // that tile's last valid ray
+  float* up;                // that tile's 128 outputs of this wave
+  float e0x, e0y, s01x, s01y, e2x, e2y, u[4], wf, w8e, w4e, of;      // what a token block, a half, a block, a pair and a quad of blocks leave for the next piece
+};
+// e' of token block tb, registers 2 h and 2 h + 1 of ray block rb
+__device__ __forceinline__ void sweep_epi_exp(SweepEpi& E, const sweep_f32x4 (&acc16)[sw::kTokBlocks][sw::kRayBlocks], float (&zs16)[sw::kTokBlocks],
+                                              const float (&ct16)[sw::kTokBlocks], const int lane_p, const int wn, const int rb, const int h, const int tb) {
+  const int r = 2 * h;
+  float ex = __builtin_amdgcn_exp2f(__builtin_fmaf(acc16[tb][rb][r], E.cfl, ct16[tb]));
+  float ey = __builtin_amdgcn_exp2f(__builtin_fmaf(acc16[tb][rb][r + 1], E.cfl, ct16[tb]));
+  if (__builtin_expect(E.lim < kBNX - 1, 0)) {                     // clamped duplicates of the last ray count as 0 (the scene's last tile alone: out of line)
+    int le = lane_p;
+    asm volatile("" : "+v"(le));
+    const int rr = wn * 128 + sw::acc_ray(le, rb, r);
+    ex = rr <= E.lim ? ex : 0.f;
+    ey = rr + 1 <= E.lim ? ey : 0.f;
+  }
+  zs16[tb] += ex + ey;
+  // (the empty asm pins a piece's additions to its slot: the ragged branch ends the basic block, and behind it the compiler sank the additions of a
+  // whole block into one place, with its 16 e' live until there)
+  asm volatile("" : "+v"(zs16[tb]));
+  if (tb == 0) {
+    E.e0x = ex, E.e0y = ey;
+  } else if (tb == 1) {
+    E.s01x = E.e0x + ex, E.s01y = E.e0y + ey;
+    asm volatile("" : "+v"(E.s01x), "+v"(E.s01y));
+  } else if (tb == 2) {
+    E.e2x = ex, E.e2y = ey;
+  } else {
+    E.u[r] = E.s01x + (E.e2x + ex), E.u[r + 1] = E.s01y + (E.e2y + ey);
+    asm volatile("" : "+v"(E.u[r]), "+v"(E.u[r + 1]));
+  }
+}
+// the butterfly of a finished block (sweep_layout.h): steps 0 and 1 (register bits, DPP) ...
+__device__ __forceinline__ void sweep_epi_fold_a(SweepEpi& E, const int lane_p) {
+  const bool lb0 = lane_p & 1, lb1 = lane_p & 2;
+  float v2[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const float keep = lb0 ? E.u[2 * i + 1] : E.u[2 * i], send = lb0 ? E.u[2 * i] : E.u[2 * i + 1];
+    v2[i] = keep + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+  }
+  const float keep = lb1 ? v2[1] : v2[0], send = lb1 ? v2[0] : v2[1];
+  E.wf = keep + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, send), 0x4E, 0xF, 0xF, true));        // quad_perm [2,3,0,1]
+}
+// ... step 2 (lane ^ 4) once the odd block of a pair is there ...
+__device__ __forceinline__ void sweep_epi_fold_b(SweepEpi& E, const int lane_p, const int rb) {
+  if (!(rb & 1)) {
+    E.w8e = E.wf;
+    return;
+  }
+  const bool lb2 = lane_p & 4;
+  const float keep = lb2 ? E.wf : E.w8e, send = lb2 ? E.w8e : E.wf;
+  E.wf = keep + __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, send), 0x101F));
+}
+// ... and step 3 (lane ^ 8) once the second pair of a quad is there: output x = rb >> 2
+__device__ __forceinline__ void sweep_epi_fold_c(SweepEpi& E, const int lane_p, const int rb) {
+  if ((rb & 3) == 1) E.w4e = E.wf;
+  if ((rb & 3) != 3) return;
+  const bool lb3 = lane_p & 8;
+  const float keep = lb3 ? E.wf : E.w4e, send = lb3 ? E.w4e : E.wf;
+  E.of = keep + __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, send), 0x201F));
+}
+__device__ __forceinline__ void sweep_epi_store(const SweepEpi& E, const int lane_p, const int x) {
+  int le = lane_p;
+  asm volatile("" : "+v"(le));
+  __builtin_nontemporal_store(E.of, E.up + (unsigned)sw::out_ray(le & 63, x));      // (a 32-bit offset of known range beside the wave's base: no 64-bit lane arithmetic)
+}
+// What step g carries behind its MFMA `slot`: the four token blocks of a half behind MFMAs 1, 3, 5, 7 (both halves: 0..3 and 4..7), the block's
+// butterfly behind 9, 10 and 11.  Output 0 leaves in step 7 (behind slab 11's barrier), output 1 in step 15 (behind slab 0's; the caller).
+__device__ __forceinline__ void sweep_epi_step(SweepEpi& E, const sweep_f32x4 (&acc16)[sw::kTokBlocks][sw::kRayBlocks], float (&zs16)[sw::kTokBlocks],
+                                               const float (&ct16)[sw::kTokBlocks], const int lane_p, const int wn, const int g, const int slot) {
+  if (g < 1 || g > 14) return;
+  const bool both = g == 1 || g == 14;
+  const int rb = g == 1 ? 0 : g == 14 ? 7 : g >> 1;
+  if (both) {
+    if (slot < 8) sweep_epi_exp(E, acc16, zs16, ct16, lane_p, wn, rb, slot >> 2, slot & 3);
+  } else if ((slot & 1) && slot < 8) {
+    sweep_epi_exp(E, acc16, zs16, ct16, lane_p, wn, rb, g & 1, slot >> 1);
+  }
+  if (both || (g & 1)) {
+    if (slot == 9) sweep_epi_fold_a(E, lane_p);
+    if (slot == 10) sweep_epi_fold_b(E, lane_p, rb);
+    if (slot == 11) {
+      sweep_epi_fold_c(E, lane_p, rb);
+      if (rb == 3) sweep_epi_store(E, lane_p, 0);
+    }
+  }
+}
 
 // TERMS: kAllTerms or kOneTerm.  OUT: what leaves the kernel (kOut*): fp32 or 24-bit fixed-point logits (see kTileBytes24),
 // statistics only, or the upper-bound column sums of the select path.  SHAPE: kMfma32, or kMfma16 (OUT == kOutUB only: the blocked logits of the
@@ -246,11 +346,24 @@ constexpr int kMfma16 = 1;     // v_mfma_f32_16x16x32_f16: 4 x 8 blocks, a slab 
 // carry the next slab's first ray block and, plane by plane as the step's MFMAs release them (the l planes after the l*h term, the h plane of
 // token block i after its h*h), the next slab's token fragments; only those last 4 reads are still in flight when the next slab starts, and
 // its first 4 MFMAs do not need them (counted lgkmcnt).  The 8 DMA pieces of a batch -- q of slab + 1, key of slab + 2 -- go into steps 0 and 1.
+//
+// kMfma16 (not kMfma16Tile): the epilogue runs block by block under slab 11 and the next tile's slab 0 (SweepEpi, above).  Its waits:
+//   vmcnt   counts loads and stores in issue order, and every counted wait of the ring is `vmcnt(4)` before a slab barrier: "q(sl + 1) has landed, only
+//           the 4 pieces of key(sl + 2) are younger".  The two 4-byte stores of a tile therefore sit BEHIND a barrier and BEFORE the next batch: output 0
+//           in step 7 of slab 11 (behind key(1') of the next tile, before q(1')), output 1 in step 7 of the next slab 0 (behind key(2'), before q(2')).
+//           A store is then always OLDER than the q pieces the next wait stands for: vmcnt(4) stays exact in slabs 11, 0 and 1, with or without
+//           stores (the first tile of a group has none pending; inactive wave rows never store).  The drain's store is followed by vmcnt(0).
+//   lgkmcnt the pieces' ds_swizzle (two per finished pair / quad of blocks, behind MFMAs 10 and 11 of a step) are builtins: the compiler waits with
+//           lgkmcnt(0) before their first use, which also lands the step's fragment reads -- never fewer than the counted waits ask for (LDS
+//           operations return in order: a wait that undercounts what is in flight only waits longer).  Step 15 (slab 0, step 7) carries a store and
+//           no swizzle, so the `lgkmcnt(4)` that lets the 4 token h planes fly into slab 1 stands as it is; slab 11 still ends with lgkmcnt(0).
+//   MFMA -> VALU: a piece reads accumulators at least one step (12 MFMAs) after their last MFMA; the compiler places what the hardware asks for.
 template <int TERMS, int OUT, bool PERS = false, int SHAPE = kMfma32>
 __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
   static_assert(TERMS == kAllTerms || TERMS == kOneTerm, "k_logits_f16x: TERMS is 3 or 1");
-  static_assert(SHAPE == kMfma32 || (SHAPE == kMfma16 && OUT == kOutUB && TERMS == kAllTerms), "k_logits_f16x: 16x16x32 is the select sweep's shape");
-  constexpr bool S16 = SHAPE == kMfma16;
+  static_assert(SHAPE == kMfma32 || ((SHAPE == kMfma16 || SHAPE == kMfma16Tile) && OUT == kOutUB && TERMS == kAllTerms), "k_logits_f16x: 16x16x32 is the select sweep's shape");
+  constexpr bool S16 = SHAPE != kMfma32;
+  constexpr bool PIPE = SHAPE == kMfma16;      // the epilogue runs block by block under the MFMAs of slab 11 and of the next tile's slab 0
   constexpr bool L24 = OUT == kOutL24;
   constexpr bool one_term = TERMS == kOneTerm;
   __shared__ __attribute__((aligned(1024))) char lds[kLdsX];
@@ -418,6 +531,18 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
     }
     wait_lds();
 
+    typedef sweep_f32x4 f32x4;
+    f32x4 acc16[sw::kTokBlocks][sw::kRayBlocks];
+    // kMfma16: the block-wise epilogue's carried state (SweepEpi, above the kernel)
+    SweepEpi E;
+    if constexpr (PIPE) {
+      E.lim = kBNX - 1;
+#pragma unroll
+      for (int i = 0; i < sw::kTokBlocks; ++i)
+#pragma unroll
+        for (int j = 0; j < sw::kRayBlocks; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+
     for (int tile = t_begin; tile < t_end; ++tile) {
       // after the last tile of the run the prefetch simply re-reads the current tile (harmless, keeps the slab loop and
       // its vmcnt bookkeeping free of branches)
@@ -499,37 +624,56 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
         }
       };
 
-      typedef float f32x4 __attribute__((ext_vector_type(4)));
-      f32x4 acc16[sw::kTokBlocks][sw::kRayBlocks];
       if (S16) {
+        const bool pend = __builtin_expect(tile > t_begin, 1);      // PIPE: blocks 4..7 of the previous tile are still to be finished
+        if constexpr (PIPE) {
+          const int t128 = min(2 * tile + wn, n_tiles128 - 1);
+          E.cfl_next = ((cq * load_uniform(A.kinv + t128)) * kInvSqrtD) * 1.4426950408889634f;
+        } else {
 #pragma unroll
-        for (int i = 0; i < sw::kTokBlocks; ++i)
+          for (int i = 0; i < sw::kTokBlocks; ++i)
 #pragma unroll
-          for (int j = 0; j < sw::kRayBlocks; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < sw::kRayBlocks; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
         // One step: ray block rb against the slab's 4 token blocks, term by term (l*h, h*l, h*h: smallest first per accumulator, and 4 MFMAs
         // between two on the same accumulator); `side(slot)` places at most one read or DMA piece behind each MFMA.
-        auto step16 = [&](f16x8& xh, const int rb, auto side) {
+        // PIPE: in slab 0 (`first`) the first term starts from the constant 0 instead of the accumulator, which the previous tile's epilogue has just read
+        auto step16 = [&](f16x8& xh, const int rb, const bool first, auto side) __attribute__((always_inline)) {
           constexpr int PQ[3] = {1, 0, 0};      // token plane and (below) ray plane of a term: 0 = h, 1 = l
 #pragma unroll
           for (int q = 0; q < 3; ++q) {
 #pragma unroll
             for (int tb = 0; tb < sw::kTokBlocks; ++tb) {
-              acc16[tb][rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q == 1 ? kl : xh, tq[tb][PQ[q]], acc16[tb][rb], 0, 0, 0);
+              if (first && q == 0) acc16[tb][rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, tq[tb][PQ[q]], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+              else acc16[tb][rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q == 1 ? kl : xh, tq[tb][PQ[q]], acc16[tb][rb], 0, 0, 0);
               side(q * 4 + tb);
               __builtin_amdgcn_sched_barrier(0);
             }
           }
         };
-#pragma unroll
-        for (int sl = 0; sl < 12; ++sl) {
-          const int qs1 = (sl + 1) & 1, kn = (sl + 1) % 3, ks2 = (sl + 2) % 3, ks3 = sl % 3;
+        // (a slab is a generic lambda over its number, not a loop body: with the epilogue pieces of slabs 0 and 11 in it, twelve copies of the
+        // not yet specialised body are beyond what the unroller takes, and the fragment reads need their stage as a constant)
+        auto slab16 = [&](auto SL) __attribute__((always_inline)) {
+          constexpr int sl = decltype(SL)::value;
+          constexpr int qs1 = (sl + 1) & 1, kn = (sl + 1) % 3, ks2 = (sl + 2) % 3, ks3 = sl % 3;
 #pragma unroll
           for (int rb = 0; rb < sw::kRayBlocks - 1; ++rb) {
             // steps 0..6: read ray block rb + 1 into the other buffer; step 0 first lets the 4 token h planes land that the previous slab's last
             // step left in flight (its slots 0..3 are the l*h term: token l planes); steps 0 and 1 carry the batch q(sl + 1) -> the q stage and
             // key(sl + 2) -> the key stage that slab sl - 1 left behind its barrier
-            step16(kh[rb & 1], rb, [&](const int slot) {
+            step16(kh[rb & 1], rb, PIPE && sl == 0, [&](const int slot) __attribute__((always_inline)) {
               if (rb == 0 && slot == 3) wait_lds();
+              if constexpr (PIPE && sl == 11) {
+                if (rb == 0 && slot == 0) {      // from here on the pieces work on THIS tile
+                  E.cfl = E.cfl_next;
+                  E.lim = lim_cur;
+                  E.up = A.ub + ((int64_t)bl * 4 + wm) * A.ub_stride + ((int64_t)tile * kBNX + wn * 128);
+                }
+                sweep_epi_step(E, acc16, zs16, ct16, lane_p, wn, rb, slot);
+              }
+              if constexpr (PIPE && sl == 0) {
+                if (pend) sweep_epi_step(E, acc16, zs16, ct16, lane_p, wn, 8 + rb, slot);
+              }
               if (slot == 4) kh[(rb + 1) & 1] = read_b16(rb + 1, 0, ks3);
               if (slot == 8) kl = read_b16(rb + 1, 1, ks3);      // (the l plane has one buffer: the h*l term, slots 4..7, was its last use)
               if (rb == 0 && slot >= 6 && slot < 10) issue_q((sl + 1) % 12, qs1, slot - 6);
@@ -545,7 +689,11 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
           asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
           __builtin_amdgcn_s_barrier();
           // step 7: the first ray block of slab sl + 1, then its token fragments as this step's terms release their registers
-          step16(kh[1], sw::kRayBlocks - 1, [&](const int slot) {
+          step16(kh[1], sw::kRayBlocks - 1, PIPE && sl == 0, [&](const int slot) __attribute__((always_inline)) {
+            if constexpr (PIPE && sl == 11) sweep_epi_step(E, acc16, zs16, ct16, lane_p, wn, 7, slot);
+            if constexpr (PIPE && sl == 0) {
+              if (pend && slot == 1) sweep_epi_store(E, lane_p, 1);
+            }
             if (slot == 0) kh[0] = read_b16(0, 0, kn);
             else if (slot >= 4 && slot < 8) tq[slot - 4][1] = read_a16(slot - 4, 1, qs1);
             if (slot == 8) kl = read_b16(0, 1, kn);      // (before the 4 reads that may stay in flight)
@@ -557,7 +705,11 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
           } else {
             wait_lds();       // the tile's last slab: everything lands before the epilogue
           }
-        }
+        };
+        slab16(std::integral_constant<int, 0>{}), slab16(std::integral_constant<int, 1>{}), slab16(std::integral_constant<int, 2>{});
+        slab16(std::integral_constant<int, 3>{}), slab16(std::integral_constant<int, 4>{}), slab16(std::integral_constant<int, 5>{});
+        slab16(std::integral_constant<int, 6>{}), slab16(std::integral_constant<int, 7>{}), slab16(std::integral_constant<int, 8>{});
+        slab16(std::integral_constant<int, 9>{}), slab16(std::integral_constant<int, 10>{}), slab16(std::integral_constant<int, 11>{});
       } else {
 #pragma unroll
       for (int sl = 0; sl < 12; ++sl) {
@@ -637,7 +789,9 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
         // by a halving butterfly over the 32 lanes of each half wave (lane bit i <-> ray-register bit 3 - i, DPP for the two
         // in-quad steps, ds_swizzle for the rest) and leave as TWO 4-byte stores per lane and tile: ray
         // 64 b4 + 32 x + 8 rg + 4 h + j of the wave's 128-ray half with 4 rg + j = bitrev4(lane & 15), h = lane >> 5.
-        if (S16) {
+        if (S16 && PIPE) {
+          // done or under way: slab 11 carried blocks 0..3, the next tile's slab 0 (or the drain behind the tile loop) takes blocks 4..7
+        } else if (S16) {
           // kMfma16 (maps: sweep_layout.h).  A lane holds ONE token of each of its 4 token blocks and, per ray block, the 4 rays 4 (lane >> 4) + reg:
           // per ray the 4 token blocks add up in registers, then the 32 values v[4 rb + reg] go through a halving butterfly over the 16 token lanes --
           // lane bit s <-> index bit s; the two register bits (DPP) as soon as a ray block is done, the two ray-block bits (ds_swizzle) at the end --
@@ -836,6 +990,19 @@ __global__ void __launch_bounds__(512, 1) k_logits_f16x(LogitsF16Args A) {
       }
       kcur = knext;
       lim_cur = lim_next;
+    }
+    if constexpr (PIPE) {
+      if (active) {      // the drain: blocks 4..7 of the group's last tile, with nothing left to hide them under
+#pragma unroll
+        for (int rb = 4; rb < sw::kRayBlocks; ++rb) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) sweep_epi_exp(E, acc16, zs16, ct16, lane_p, wn, rb, k >> 2, k & 3);
+          sweep_epi_fold_a(E, lane_p);
+          sweep_epi_fold_b(E, lane_p, rb);
+          sweep_epi_fold_c(E, lane_p, rb);
+        }
+        sweep_epi_store(E, lane_p, 1);
+      }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the trailing prefetch
   }
@@ -2281,6 +2448,13 @@ bool sweep_mfma16() {
   const char* e = getenv("SIXDGS_SWEEP_MFMA");
   return !(e && atoi(e) == 32);
 }
+// Where the 16x16x32 sweep runs its epilogue: block by block under the MFMAs of slab 11 and the next tile's slab 0 (default), or
+// SIXDGS_SWEEP_EPILOGUE=tile for the whole epilogue behind the tile's last slab (developer switch, same bits either way: the A/B of
+// profiles/sweep_epilogue_pipelined.md and what tests/test_gpu_sweep_epilogue.py compares against; read at every launch)
+bool sweep_epilogue_tile() {
+  const char* e = getenv("SIXDGS_SWEEP_EPILOGUE");
+  return e && e[0] == 't' && e[1] == 'i' && e[2] == 'l' && e[3] == 'e' && e[4] == 0;
+}
 int sibling_sync_cus() {
   static int cus = -1;
   if (cus < 0) {
@@ -2462,7 +2636,8 @@ int sixdgs_select_sweep(const float* q, const int32_t* d_n_tok, const int32_t* h
         grid = (unsigned)(V.n_sets * ns);
       }
       SdgProfileScope scope(prof, s, 2.0 * tok * SIXDGS_D * (double)r, (double)r * (kRowF + T.n_images * 16.0));
-      auto kern = sweep_mfma16() ? (V.n_sets > 0 ? k_logits_f16x<kAllTerms, kOutUB, true, kMfma16> : k_logits_f16x<kAllTerms, kOutUB, false, kMfma16>)
+      auto kern = sweep_mfma16() ? (sweep_epilogue_tile() ? (V.n_sets > 0 ? k_logits_f16x<kAllTerms, kOutUB, true, kMfma16Tile> : k_logits_f16x<kAllTerms, kOutUB, false, kMfma16Tile>)
+                                                          : (V.n_sets > 0 ? k_logits_f16x<kAllTerms, kOutUB, true, kMfma16> : k_logits_f16x<kAllTerms, kOutUB, false, kMfma16>))
                                  : (V.n_sets > 0 ? k_logits_f16x<kAllTerms, kOutUB, true> : k_logits_f16x<kAllTerms, kOutUB, false>);
       hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, s, V);
     }
