@@ -1,10 +1,14 @@
-"""render_views -- synthetic query views of a GaussianScene (ops.splat_views: the Gaussians as z-buffered flat discs).
+"""render_views -- views of a GaussianScene, by one of two renderers:
+
+  "disc"    ops.splat_views: the Gaussians as z-buffered flat discs (the default; described below)
+  "raster"  ops.raster_views: the alpha-blended 3DGS forward rasteriser -- anisotropic footprints from each Gaussian's scale and
+            rotation, its opacity, front-to-back blending over 16 x 16 tiles; the views the scene's own renderer gives
 
 No real scenes or checkpoints ship with this build, and `synthetic.make_cameras` fills its images with random bytes: nothing in them
 depends on the camera, so a scorer cannot learn a pose from them.  The views rendered here do depend on it -- every pixel carries the SH
 colour of the nearest Gaussian towards the camera, the colour the ray emitter gives a ray from that Gaussian to the camera -- which is
-what training a stand-in scene needs.  This is a stand-in view generator, not the 3DGS rasteriser (no blending, no anisotropic
-footprints, no anti-aliasing).
+what training a stand-in scene needs.  The disc renderer is a stand-in view generator, not the 3DGS rasteriser (no blending, no
+anisotropic footprints, no anti-aliasing); renderer="raster" is that rasteriser.
 
 The camera of a rendered view is the camera `test.gt_pose_and_intrinsics` derives from the same CameraInfo (w2c = [R^T | T],
 fx = fov2focal(FovX, width), principal point at the image centre): the image and the ground-truth pose of the loss and of the error
@@ -49,11 +53,18 @@ def _as_camera_info(cam, image) -> CameraInfo:
 
 @torch.no_grad()
 def render_views(scene: GaussianScene, cameras: Sequence, *, rgba: bool = False, extent: float = 1.0, near_z: float = 0.05,
-                 background=(1.0, 1.0, 1.0), batch_size: Optional[int] = None, return_device: bool = False) -> List[CameraInfo]:
+                 background=(1.0, 1.0, 1.0), batch_size: Optional[int] = None, return_device: bool = False, renderer: str = "disc",
+                 scale_modifier: float = 1.0) -> List[CameraInfo]:
     """New CameraInfos (same poses and intrinsics) whose `image` is the rendered uint8 array [height, width, 3 | 4].
     cameras: CameraInfos or the dicts of synthetic.make_cameras.  rgba: alpha 255 on covered pixels, 0 on the background, so that the
     backbone wrapper's mask -> token selection sees the silhouette.  Views of one size are rendered `batch_size` per launch (default: as
-    many as fit WORKSPACE_BUDGET); the images do not depend on it.  return_device: also return the images as uint8 GPU tensors."""
+    many as fit WORKSPACE_BUDGET); the images do not depend on it.  return_device: also return the images as uint8 GPU tensors.
+    renderer="raster": the 3DGS rasteriser instead of the discs; it uses the scene's rotations and opacities and scale_modifier, ignores
+    extent and near_z (its near plane is 0.2), and with rgba the alpha channel is round(255 (1 - T))."""
+    if renderer not in ("disc", "raster"):
+        raise ValueError(f"renderer must be 'disc' or 'raster' (got {renderer!r})")
+    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
+        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
     if not (float(extent) > 0.0 and float(extent) < float("inf")):
         raise ValueError(f"extent must be positive and finite (got {extent})")
     if not float(near_z) >= 0.0:
@@ -70,6 +81,21 @@ def render_views(scene: GaussianScene, cameras: Sequence, *, rgba: bool = False,
     images: List[Optional[torch.Tensor]] = [None] * len(cameras)
     for size in sorted(set(sizes)):
         which = [i for i, s in enumerate(sizes) if s == size]
+        if renderer == "raster":
+            per_view = max(ops.raster_views_workspace_bytes(n, 1, *size, ops.raster_instances_estimate(n, 1)), 1)
+            step = int(batch_size) if batch_size is not None else max(1, WORKSPACE_BUDGET // per_view)
+            per_view_instances = ops.raster_instances_estimate(n, 1)
+            for b0 in range(0, len(which), step):
+                part = which[b0:b0 + step]
+                img, needed = ops.raster_views(scene._xyz, scene._scaling, scene._rotation, scene._opacity, scene._features_dc,
+                                               scene._features_rest, scene.active_sh_degree, torch.from_numpy(rows[part]).to(dev), size[0], size[1],
+                                               channels=4 if rgba else 3, scale_modifier=scale_modifier, background=background,
+                                               max_instances=min(per_view_instances * len(part), ops.RASTER_MAX_INSTANCES), want_instances=True)
+                # the next batch starts from what this one needed (plus a quarter), so that only the first one can run twice
+                per_view_instances = max(per_view_instances, -(-needed // len(part)) * 5 // 4)
+                for j, i in enumerate(part):
+                    images[i] = img[j]
+            continue
         per_view = max(ops.splat_views_workspace_bytes(n, 1, *size), 1)
         step = int(batch_size) if batch_size is not None else max(1, WORKSPACE_BUDGET // per_view)
         workspace = torch.empty(ops.splat_views_workspace_bytes(n, min(step, len(which)), *size), dtype=torch.uint8, device=dev)

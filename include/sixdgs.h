@@ -179,6 +179,53 @@ int sixdgs_splat_views(const float* xyz, const float* scale, int scale_is_log, c
                        sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Scene views by the alpha-blended 3DGS forward rasteriser (additive in ABI 10; forward only, no gradients).  With
+ * cx = width / 2, cy = height / 2 this is the image of the reference's rasteriser call in gaussian_renderer/__init__.py
+ * (prefiltered = False, SHs converted inside).  The tile is 16 x 16 pixels and is PART OF THE DEFINITION: the grid is
+ * gx = ceil(width / 16), gy = ceil(height / 16).  All arithmetic in fp32.  Per view (one row of cams) and Gaussian i:
+ *   1. p = W xyz_i + t with [W | t] the view's w2c; culled unless p.z > 0.2;
+ *   2. Sigma = R S S^T R^T, R = the rotation of rot_i = (w, x, y, z) (normalised, as the emitters do), S = diag(scale_modifier s_i),
+ *      s_i = exp(scale_i) when scale_is_log != 0, scale_i otherwise;
+ *   3. tanx = width / (2 fx), tany = height / (2 fy); tx = clamp(p.x / p.z, +-1.3 tanx) p.z, ty likewise;
+ *      J = [[fx / p.z, 0, -fx tx / p.z^2], [0, fy / p.z, -fy ty / p.z^2]]; cov = (J W) Sigma (J W)^T;
+ *      a = cov00 + 0.3, b = cov01, c = cov11 + 0.3;
+ *   4. det = a c - b^2, culled when det == 0; conic = (c / det, -b / det, a / det);
+ *   5. mid = (a + c) / 2, lambda = mid + sqrt(max(0.1, mid^2 - det)), radius = ceil(3 sqrt(lambda)) (stored saturated at 2^30);
+ *   6. centre u = fx p.x / p.z + cx, v = fy p.y / p.z + cy; the centre of pixel (x, y) is (x + 0.5, y + 0.5);
+ *   7. tile rectangle on (u - 0.5, v - 0.5): x0 = clamp(int((u - 0.5 - radius) / 16), 0, gx),
+ *      x1 = clamp(int((u - 0.5 + radius + 15) / 16), 0, gx), y0 and y1 likewise with gy (int() truncates towards zero); culled when
+ *      (x1 - x0)(y1 - y0) == 0.  Gaussian i CONTRIBUTES ONLY TO PIXELS OF TILES IN [x0, x1) x [y0, y1);
+ *   8. colour = the emitters' SH colour (a10: + 0.5, clamped below at 0, not above) for direction normalize(xyz_i - camera centre);
+ *   9. o = sigmoid(opacity_i) when opacity_is_logit != 0, opacity_i otherwise;
+ *  10. per pixel the contributing Gaussians are ordered by ascending bits of p.z, equal bits -> the smaller index first;
+ *  11. blend: T = 1, C = 0, then in that order: d = (u - x - 0.5, v - y - 0.5),
+ *      power = -0.5 (conic.x d.x^2 + conic.z d.y^2) - conic.y d.x d.y; skip when power > 0; alpha = min(0.99, o exp(power)); skip when
+ *      alpha < 1/255; T' = T (1 - alpha); when T' < 1e-4 stop (this Gaussian is not added); otherwise C += colour alpha T, T = T'.
+ *      Pixel = C + T background, alpha = 1 - T.
+ * Outputs, each may be NULL: image_f32 [views][height][width][4] (rgb, 1 - T); image_u8 [views][height][width][channels], channels 3 or
+ * 4, round(255 clamp(., 0, 1)); radii [views][n] int32, 0 = culled.  The same input gives the same bytes on every call, and a view's
+ * image does not depend on the other views of the call.
+ *
+ * A (view, Gaussian) pair takes one INSTANCE per tile of its rectangle.  The caller sizes the instance buffers with max_instances
+ * (>= 1); `instances` (device, may be NULL) receives the number the scene needs.  When that exceeds max_instances nothing is written
+ * out of bounds, the later kernels read the count on the device and return, and the images are unspecified (radii are still written):
+ * call again with max_instances >= *instances.  The sort always runs over max_instances slots, so a tight value is also the fast one.
+ * Limits: n < 2^31, views <= 65535, width, height <= 16384, views gx gy < 2^31, max_instances < 2^31, scale_modifier > 0.
+ * sixdgs_raster_views_workspace_bytes is answered without touching a GPU (0 for sizes outside the limits): the per-(view, Gaussian)
+ * records (64 B), the tile ranges, two key and two index buffers of max_instances (24 B per instance) and the temporary storage of
+ * the library scan and sort, reserved by a bound (1 MiB + 2 B per record, 1 MiB + 16 B per instance); if the installed rocPRIM asks
+ * for more the call returns SIXDGS_E_WORKSPACE.  SIXDGS_E_BADARG without a launch for argument errors; views == 0 returns 0; with n == 0
+ * the image is the background.  prof (may be NULL) receives one slot per stage: project, scan, emit, sort, ranges, blend. */
+size_t sixdgs_raster_views_workspace_bytes(int64_t n, int views, int width, int height, int64_t max_instances);
+int sixdgs_raster_views(const float* xyz, const float* scale, int scale_is_log, const float* rot /*[N,4] (w,x,y,z)*/,
+                        const float* opacity /*[N]*/, int opacity_is_logit, const float* f_dc, const float* f_rest, int sh_degree,
+                        int n_coef, int64_t n, const float* cams /*[views][16]: w2c rows 0..2 (12 floats), fx, fy, cx, cy*/,
+                        int views, int width, int height, float scale_modifier, const float* background /*[3] device*/,
+                        float* image_f32, uint8_t* image_u8, int channels /*3 or 4*/, int32_t* radii, int64_t max_instances,
+                        int64_t* instances /*[1] device or NULL*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream,
+                        sixdgs_profile* prof);
+
+/* ---------------------------------------------------------------------------------------------
  * Scorer, scene side (once per scene): ray MLP + k_proj -> key cache
  * replaces RayPreprocessor.forward (ray_preprocessor.py:36-46) + k_proj (our_multihead_attention.py:74)
  * ------------------------------------------------------------------------------------------- */

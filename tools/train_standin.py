@@ -1,6 +1,6 @@
 """Train the scorer on rendered views of a stand-in scene and look at the inference path on the trained weights.
 
-    python tools/train_standin.py [--gaussians 5000] [--iterations 1500] [--size 224] [--out profiles/trained_standin.md]
+    python tools/train_standin.py [--gaussians 5000] [--iterations 1500] [--size 224] [--renderer disc|raster] [--out profiles/trained_standin.md]
 
 Builds synthetic.make_scene, renders training and held-out views with render_views (6dgs_amd/render.py), records the per-view pose
 errors of test_pose_estimation with the initial weights, trains with train_id_module(batched_window=True) on the reference's schedule
@@ -47,12 +47,12 @@ def fresh_scorer(seed: int = 0):
     return idm.cuda()
 
 
-def build_standin(n_gauss: int, seed: int, n_train: int, n_held: int, size: int, extent: float = 1.0):
+def build_standin(n_gauss: int, seed: int, n_train: int, n_held: int, size: int, extent: float = 1.0, renderer: str = "disc"):
     """-> (GaussianScene, rendered training views, rendered held-out views): cameras of make_cameras with different seeds."""
     pkg, syn, _, _ = modules()
     scene = pkg.GaussianScene.from_dict(syn.make_scene(n_gauss, seed), device="cuda")
-    train = pkg.render_views(scene, syn.make_cameras(n_train, seed + 100, width=size, height=size), extent=extent)
-    held = pkg.render_views(scene, syn.make_cameras(n_held, seed + 200, width=size, height=size), extent=extent)
+    train = pkg.render_views(scene, syn.make_cameras(n_train, seed + 100, width=size, height=size), extent=extent, renderer=renderer)
+    held = pkg.render_views(scene, syn.make_cameras(n_held, seed + 200, width=size, height=size), extent=extent, renderer=renderer)
     return scene, train, held
 
 
@@ -296,7 +296,7 @@ def report(args, cmd, loss, errs, parity, render_ms, seconds, test_seconds=None)
          f"Command: `{cmd}`", "",
          f"Inputs: `make_scene({args.gaussians}, {args.seed})`, {args.train_views} training and {args.held_views} held-out views of "
          f"`make_cameras` (seeds {args.seed + 100} / {args.seed + 200}, {args.size} x {args.size}, FoV 0.8) rendered by `render_views` "
-         f"(extent {args.extent}); random-init ViT-S/14 (`SIXDGS_RANDOM_BACKBONE=1`), scorer initialised from `make_scorer_state_dict(0, with_cnn=True)`; "
+         f"(renderer {args.renderer!r}, extent {args.extent}); random-init ViT-S/14 (`SIXDGS_RANDOM_BACKBONE=1`), scorer initialised from `make_scorer_state_dict(0, with_cnn=True)`; "
          f"`train_id_module(batched_window=True)`, {args.iterations} iterations x {args.accumulation} images, rays renewed every {args.renewal} "
          f"(1000-ellipsoid emission).  Pose errors: `test_pose_estimation` on one fixed emission ({errs['rays']} rays), the same before and after.", "",
          "## Training", "",
@@ -348,6 +348,8 @@ def main():
     ap.add_argument("--held-views", type=int, default=16)
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--extent", type=float, default=1.0)
+    ap.add_argument("--renderer", choices=["disc", "raster"], default="disc",
+                    help="disc: z-buffered flat discs (ops.splat_views); raster: the alpha-blended 3DGS rasteriser (ops.raster_views)")
     ap.add_argument("--iterations", type=int, default=1500)
     ap.add_argument("--accumulation", type=int, default=32)
     ap.add_argument("--renewal", type=int, default=10)
@@ -364,7 +366,7 @@ def main():
     checker.build()
     pkg, _, _, _ = modules()
     torch.manual_seed(0)
-    scene, train_cams, held_cams = build_standin(args.gaussians, args.seed, args.train_views, args.held_views, args.size, args.extent)
+    scene, train_cams, held_cams = build_standin(args.gaussians, args.seed, args.train_views, args.held_views, args.size, args.extent, args.renderer)
     idm = fresh_scorer().eval()
     rays = pkg.generate_all_possible_rays(scene)
     up = model_up_of(train_cams)
