@@ -25,6 +25,7 @@ from .scene import CameraInfo  # noqa: F401
 from .distance_based_loss import DistanceBasedScoreLoss  # noqa: F401
 from .train import train_id_module  # noqa: F401
 from .render import render_views  # noqa: F401
+from .autograd import raster_views  # noqa: F401
 
 __all__ = ["GaussianModel", "GaussianScene", "CameraInfo", "generate_all_possible_rays", "IdentificationModule",
-           "test_pose_estimation", "DistanceBasedScoreLoss", "train_id_module", "render_views"]
+           "test_pose_estimation", "DistanceBasedScoreLoss", "train_id_module", "render_views", "raster_views"]

@@ -81,3 +81,36 @@ def ray_mlp(rp, x: torch.Tensor) -> torch.Tensor:
     w3, hid = rp.mlp2[0].weight, rp.mlp[2].weight.shape[0]
     z = linear(h, w3[:, :hid], rp.mlp2[0].bias) + linear(x, w3[:, hid:], None)
     return linear(torch.relu(z), rp.mlp2[2].weight, rp.mlp2[2].bias)
+
+
+class RasterViews(torch.autograd.Function):
+    """image_f32 of ops.raster_views, differentiable in the six scene tensors and cams (ops.raster_views_backward).  ctx keeps the
+    forward's workspace: the backward reads the records, the tile ranges and the sorted instances from it, no second sort."""
+
+    @staticmethod
+    def forward(ctx, xyz, scale, rot, opacity, f_dc, f_rest, cams, sh_degree, width, height, kw):
+        image, state = ops.raster_views(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree, cams, width, height, want_float=True,
+                                        want_u8=False, want_state=True, **kw)
+        ctx.save_for_backward(xyz, scale, rot, opacity, f_dc, f_rest, cams)
+        ctx.state, ctx.args = state, (sh_degree, width, height, {k: v for k, v in kw.items() if k != "max_instances"})
+        return image
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        inputs = ctx.saved_tensors
+        sh_degree, width, height, kw = ctx.args
+        want = tuple(name for name, need in zip(ops.RASTER_GRADIENTS, ctx.needs_input_grad[:7]) if need)
+        if not want:
+            return (None,) * 11
+        grads = ops.raster_views_backward(*inputs[:6], sh_degree, inputs[6], width, height, grad_image, ctx.state, want=want, **kw)
+        return tuple(None if g is None else g.to(x.dtype) for g, x in zip(grads, inputs)) + (None,) * 4
+
+
+def raster_views(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: torch.Tensor, width: int, height: int, *, background,
+                 scale_modifier: float = 1.0, scale_is_log: bool = True, opacity_is_logit: bool = True, max_instances=None):
+    """The float image [V,height,width,4] (rgb, 1 - T) of ops.raster_views, differentiable in xyz, scale, rot, opacity, f_dc, f_rest
+    and cams [V,16] (the 12 w2c entries as free numbers, fx, fy, cx, cy); the gradient is the one sixdgs_raster_views_backward in
+    include/sixdgs.h defines.  The forward retries on an instance overflow as ops.raster_views does."""
+    kw = dict(background=tuple(float(b) for b in background), scale_modifier=float(scale_modifier), scale_is_log=bool(scale_is_log),
+              opacity_is_logit=bool(opacity_is_logit), max_instances=max_instances)
+    return RasterViews.apply(xyz, scale, rot, opacity, f_dc, f_rest, cams, int(sh_degree), int(width), int(height), kw)

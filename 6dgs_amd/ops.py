@@ -347,13 +347,15 @@ def raster_instances_estimate(n: int, views: int) -> int:
 def raster_views(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: torch.Tensor, width: int, height: int, channels: int = 3,
                  scale_modifier: float = 1.0, background=(1.0, 1.0, 1.0), want_float: bool = False, want_u8: bool = True,
                  want_radii: bool = False, want_instances: bool = False, scale_is_log: bool = True, opacity_is_logit: bool = True,
-                 max_instances: Optional[int] = None, workspace: Optional[torch.Tensor] = None, profile: Optional[Profile] = None):
+                 max_instances: Optional[int] = None, workspace: Optional[torch.Tensor] = None, profile: Optional[Profile] = None,
+                 want_state: bool = False):
     """Views of the scene by the alpha-blended 3DGS forward rasteriser (sixdgs_raster_views in include/sixdgs.h defines the image
     operation by operation).  cams [V,16] = w2c rows 0..2 (12 floats), fx, fy, cx, cy per view; opacity [N] or [N,1].
     Returns, in this order and as far as asked for: the float image [V,height,width,4] (rgb, 1 - T: want_float), the uint8 image
     [V,height,width,channels] (want_u8), radii int32 [V,N] (want_radii), the number of tile instances the scene needed (want_instances);
     one value alone is returned bare.  The call runs with a capacity estimate (or max_instances), reads the needed count -- one
-    synchronisation -- and on overflow runs once more with the exact size."""
+    synchronisation -- and on overflow runs once more with the exact size.  want_state appends the forward's state for
+    raster_views_backward: (the workspace tensor the call ran in, the capacity it ran with)."""
     if channels not in (3, 4):
         raise ValueError(f"channels must be 3 or 4 (got {channels})")
     if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
@@ -364,7 +366,7 @@ def raster_views(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: t
         raise ValueError(f"cams must be a [views,16] tensor (got {tuple(cams.shape) if torch.is_tensor(cams) else type(cams).__name__})")
     if len(background) != 3:
         raise ValueError("background must have 3 entries")
-    if not (want_float or want_u8 or want_radii or want_instances):
+    if not (want_float or want_u8 or want_radii or want_instances or want_state):
         raise ValueError("nothing asked for: want_float, want_u8, want_radii and want_instances are all off")
     if max_instances is not None and not 1 <= int(max_instances) <= RASTER_MAX_INSTANCES:
         raise ValueError(f"max_instances must be in [1, 2^31) (got {max_instances})")
@@ -403,8 +405,72 @@ def raster_views(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: t
         if attempt == 1 or needed > RASTER_MAX_INSTANCES:
             raise RuntimeError(f"6dgs_amd: raster_views needs {needed} tile instances per launch (limit 2^31 - 1): render fewer views at once")
         capacity = needed
-    out = [o for o, want in ((image_f, want_float), (image_u, want_u8), (radii, want_radii), (needed, want_instances)) if want]
+    out = [o for o, want in ((image_f, want_float), (image_u, want_u8), (radii, want_radii), (needed, want_instances),
+                             ((ws, capacity), want_state)) if want]
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def raster_views_backward_workspace_bytes(n: int, views: int, width: int, height: int, max_instances: int) -> int:
+    return int(_lib.load().sixdgs_raster_views_backward_workspace_bytes(int(n), int(views), int(width), int(height), int(max_instances)))
+
+
+RASTER_GRADIENTS = ("xyz", "scale", "rot", "opacity", "f_dc", "f_rest", "cams")
+
+
+@_on_device
+def raster_views_backward(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: torch.Tensor, width: int, height: int,
+                          grad_image: torch.Tensor, state, scale_modifier: float = 1.0, background=(1.0, 1.0, 1.0),
+                          scale_is_log: bool = True, opacity_is_logit: bool = True, want=RASTER_GRADIENTS,
+                          workspace: Optional[torch.Tensor] = None, profile: Optional[Profile] = None):
+    """The gradients of raster_views' float image (sixdgs_raster_views_backward in include/sixdgs.h defines them): grad_image
+    [V,height,width,4] = dL / d image_f32; state = (workspace, capacity) of a raster_views(..., want_state=True) call on the same
+    arguments, not written since.  Returns a tuple in the order of RASTER_GRADIENTS -- d xyz [N,3], d scale [N,3], d rot [N,4],
+    d opacity (the shape of opacity), d f_dc, d f_rest (their shapes), d cams [V,16] -- with None for the names not in `want`."""
+    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
+        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
+    if int(width) < 1 or int(height) < 1:
+        raise ValueError(f"width and height must be positive (got {width} x {height})")
+    if not torch.is_tensor(cams) or cams.dim() != 2 or cams.shape[1] != 16:
+        raise ValueError(f"cams must be a [views,16] tensor (got {tuple(cams.shape) if torch.is_tensor(cams) else type(cams).__name__})")
+    if len(background) != 3:
+        raise ValueError("background must have 3 entries")
+    want = tuple(want)
+    if not want or any(w not in RASTER_GRADIENTS for w in want):
+        raise ValueError(f"want must name some of {RASTER_GRADIENTS} (got {want})")
+    if (not isinstance(state, (tuple, list)) or len(state) != 2 or not torch.is_tensor(state[0])
+            or not 1 <= int(state[1]) <= RASTER_MAX_INSTANCES):
+        raise ValueError("state must be the (workspace, capacity) pair of raster_views(..., want_state=True)")
+    fwd_ws, capacity = state[0], int(state[1])
+    xyz, scale, rot, opacity, f_dc, f_rest, cams = _f32(xyz), _f32(scale), _f32(rot), _f32(opacity), _f32(f_dc), _f32(f_rest), _f32(cams)
+    n, views = xyz.shape[0], cams.shape[0]
+    width, height = int(width), int(height)
+    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
+    if (xyz.shape != (n, 3) or scale.shape != (n, 3) or rot.shape != (n, 4) or opacity.numel() != n or f_dc.numel() != 3 * n
+            or f_rest.numel() != 3 * n * (n_coef - 1)):
+        raise ValueError("scene arrays disagree about the number of Gaussians")
+    if not torch.is_tensor(grad_image) or tuple(grad_image.shape) != (views, height, width, 4):
+        raise ValueError(f"grad_image must be a [{views},{height},{width},4] tensor")
+    grad_image = _f32(grad_image)
+    _need_gpu(xyz, scale, rot, opacity, f_dc, f_rest, cams, grad_image, fwd_ws, workspace)
+    lib = _lib.load()
+    dev = xyz.device
+    need = lib.sixdgs_raster_views_backward_workspace_bytes(n, views, width, height, capacity)
+    if need == 0 and views > 0:
+        raise ValueError(f"sizes outside the rasteriser's limits (n {n}, views {views}, {width} x {height}, instances {capacity})")
+    ws = workspace
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    bg = torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
+    like = {"xyz": xyz, "scale": scale, "rot": rot, "opacity": opacity, "f_dc": f_dc, "f_rest": f_rest, "cams": cams}
+    # (views == 0 launches nothing: zeros are the sum over no views)
+    out = {k: (torch.zeros_like(like[k]) if views == 0 else torch.empty_like(like[k])) for k in want}
+    check(lib.sixdgs_raster_views_backward(_p(xyz), _p(scale), int(scale_is_log), _p(rot), _p(opacity), int(opacity_is_logit), _p(f_dc),
+                                           _p(f_rest if n_coef > 1 else None), int(sh_degree), int(n_coef), n, _p(cams), views, width,
+                                           height, float(scale_modifier), _p(bg), _p(grad_image), capacity, _p(fwd_ws),
+                                           fwd_ws.numel() * fwd_ws.element_size(), *[_p(out.get(k)) for k in RASTER_GRADIENTS],
+                                           _p(ws), ws.numel() * ws.element_size(), _stream(), profile),
+          "raster_views_backward")
+    return tuple(out.get(k) for k in RASTER_GRADIENTS)
 
 
 # ---------------------------------------------------------------------------------------------

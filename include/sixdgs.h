@@ -179,7 +179,7 @@ int sixdgs_splat_views(const float* xyz, const float* scale, int scale_is_log, c
                        sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Scene views by the alpha-blended 3DGS forward rasteriser (additive in ABI 10; forward only, no gradients).  With
+ * Scene views by the alpha-blended 3DGS forward rasteriser (additive in ABI 10; its gradients: sixdgs_raster_views_backward below).  With
  * cx = width / 2, cy = height / 2 this is the image of the reference's rasteriser call in gaussian_renderer/__init__.py
  * (prefiltered = False, SHs converted inside).  The tile is 16 x 16 pixels and is PART OF THE DEFINITION: the grid is
  * gx = ceil(width / 16), gy = ceil(height / 16).  All arithmetic in fp32.  Per view (one row of cams) and Gaussian i:
@@ -224,6 +224,57 @@ int sixdgs_raster_views(const float* xyz, const float* scale, int scale_is_log, 
                         float* image_f32, uint8_t* image_u8, int channels /*3 or 4*/, int32_t* radii, int64_t max_instances,
                         int64_t* instances /*[1] device or NULL*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream,
                         sixdgs_profile* prof);
+
+/* ---------------------------------------------------------------------------------------------
+ * The rasteriser's backward (additive in ABI 10): the derivative of image_f32 of sixdgs_raster_views by every Gaussian parameter and
+ * by the camera rows.  Given grad_image [views][height][width][4] = dL / d image_f32 (rgb and 1 - T), each output is the sum over views
+ * and pixels of grad_image . d image_f32 / d theta, where image_f32 is the function of steps 1 - 11 above with EVERY DISCRETE OUTCOME
+ * HELD AT WHAT THE FORWARD TOOK: the culls of steps 1, 4 and 7; the radius and the tile rectangle (a Gaussian has no gradient from
+ * pixels outside its rectangle); the order of step 10; the two skips and the stop of step 11.  The Gaussian that triggers the stop, and
+ * everything behind it, gets nothing from that pixel; the T in C + T background and in 1 - T is the T before the stopping Gaussian.
+ * Continuous clamps differentiate as clamps, with derivative 0 where they act: min(0.99, o exp(power)); the +-1.3 tan clamp of
+ * p.x / p.z and p.y / p.z in step 3 (tx then depends on p.z only through the product, and on fx through tanx); max(colour + 0.5, 0);
+ * the 1e-12 floors of the quaternion normalisation and of the view direction.  Differentiated through: both quaternion normalisations
+ * of step 2; the normalisation of the view direction, so the colour's dependence on xyz and on the camera centre -W^T t counts; exp of
+ * the scale when scale_is_log; the sigmoid when opacity_is_logit.  scale_modifier and background are constants; behaviour exactly at a
+ * clamp's edge is unspecified; the uint8 image has no gradient.  All arithmetic in fp32.
+ *
+ * Per pixel, with 1 - T taken as a fourth channel of colour 1 and background 0, so that channel_ch = sum_j c_j,ch alpha_j T_j +
+ * T_fin bg_ch over the Gaussians j the pixel blended (T_j = the T before j, T_fin = the final T) and g = the pixel's grad_image:
+ *   dL / d alpha_j = sum_ch g_ch (c_j,ch T_j - R_j,ch / (1 - alpha_j)),  R_j,ch = sum_{k > j} c_k,ch alpha_k T_k + T_fin bg_ch,
+ *   dL / d c_j,ch  = g_ch alpha_j T_j for the three real channels,
+ * walked back to front: R accumulates, T_j = T_{j+1} / (1 - alpha_j).  Where alpha_j is not clamped, d alpha_j / d o = exp(power) and
+ * d alpha_j / d power = alpha_j; power gives d u, d v and d conic.  Per (view, Gaussian) these nine numbers (d u, d v, 3 conic, d o,
+ * 3 colour) are summed over the pixels of a tile in a fixed tree (the 256 pixels in 4 groups of 64 rows-of-16 order, within a group
+ * x += x_(l xor s), s = 32 .. 1, then the groups in order; a group none of whose pixels blended j is left out), then over the tiles of
+ * the rectangle in rectangle order, then chained through steps 9 .. 1 to the parameters.
+ *
+ * Outputs, each may be NULL, WRITTEN, NOT ACCUMULATED: d_xyz [n,3]; d_scale [n,3] with respect to the array as given (log or not);
+ * d_rot [n,4]; d_opacity [n] (logit or not); d_f_dc [n,1,3]; d_f_rest [n,n_coef-1,3] (zeros for coefficients above sh_degree);
+ * d_cams [views][16]: the 12 w2c entries as free numbers, then fx, fy, cx, cy.  A Gaussian that contributes to no pixel gets exact zeros.
+ * SAME INPUT, SAME BYTES: no floating-point atomics anywhere.  VIEWS DO NOT MIX: row v of d_cams is the same bits whether view v is
+ * differentiated alone or in a batch (per view: Gaussians in blocks of 256, the fixed tree inside a block, then the blocks in order),
+ * and a Gaussian's gradient over a batch is its per-view gradients, each chained to parameter space within its view, added in ascending
+ * view order: ((g_0 + g_1) + g_2) ...
+ *
+ * fwd_ws is the workspace of a COMPLETED sixdgs_raster_views call with the same scene, cams, sizes, scale_modifier and max_instances,
+ * whose instance count fitted, not written since (whether that call produced an image does not matter).  The backward reads from it the
+ * per-(view, Gaussian) records, the rectangles, the scanned offsets, the tile ranges and the sorted indices (the forward leaves a word
+ * in it that says which of its two index buffers holds them) -- no second sort; the library stays stateless and fwd_ws is not
+ * written.  If the recorded total exceeds max_instances the kernels read that on the device and return; the outputs are then
+ * unspecified.  views == 0 returns 0; n == 0 writes zero d_cams.  Limits and argument errors are the forward's, plus NULL grad_image /
+ * fwd_ws and too small a fwd_ws_bytes: SIXDGS_E_BADARG / SIXDGS_E_WORKSPACE without touching a GPU.  Two calls on the same inputs may
+ * run concurrently on different streams with different ws.  Workspace (answered without a GPU, 0 outside the limits): 36 B per
+ * instance (max_instances x 9 floats) + 64 B per view and block of 256 Gaussians.  prof (may be NULL) receives one slot per stage:
+ * blend_bwd, project_bwd, cams. */
+size_t sixdgs_raster_views_backward_workspace_bytes(int64_t n, int views, int width, int height, int64_t max_instances);
+int sixdgs_raster_views_backward(const float* xyz, const float* scale, int scale_is_log, const float* rot, const float* opacity,
+                                 int opacity_is_logit, const float* f_dc, const float* f_rest, int sh_degree, int n_coef, int64_t n,
+                                 const float* cams, int views, int width, int height, float scale_modifier,
+                                 const float* background /*[3] device*/, const float* grad_image /*[views][height][width][4]*/,
+                                 int64_t max_instances, const void* fwd_ws, size_t fwd_ws_bytes, float* d_xyz, float* d_scale,
+                                 float* d_rot, float* d_opacity, float* d_f_dc, float* d_f_rest, float* d_cams /*[views][16]*/,
+                                 void* ws, size_t ws_bytes, sixdgs_stream_t stream, sixdgs_profile* prof);
 
 /* ---------------------------------------------------------------------------------------------
  * Scorer, scene side (once per scene): ray MLP + k_proj -> key cache
