@@ -25,7 +25,9 @@ from .scene import CameraInfo  # noqa: F401
 from .distance_based_loss import DistanceBasedScoreLoss  # noqa: F401
 from .train import train_id_module  # noqa: F401
 from .render import render_views  # noqa: F401
-from .autograd import raster_views  # noqa: F401
+from .autograd import photometric_loss, raster_views  # noqa: F401
+from .refine import refine_poses, refine_results  # noqa: F401
 
 __all__ = ["GaussianModel", "GaussianScene", "CameraInfo", "generate_all_possible_rays", "IdentificationModule",
-           "test_pose_estimation", "DistanceBasedScoreLoss", "train_id_module", "render_views", "raster_views"]
+           "test_pose_estimation", "DistanceBasedScoreLoss", "train_id_module", "render_views", "raster_views", "photometric_loss",
+           "refine_poses", "refine_results"]

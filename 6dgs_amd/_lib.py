@@ -59,6 +59,8 @@ SIGNATURES = {
     "sixdgs_raster_views_backward_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
     "sixdgs_raster_views_backward": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, i32, i32, C.c_float, vp, vp, i64, vp, sz,
                                            vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Profile)]),
+    "sixdgs_photometric_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "sixdgs_photometric_loss": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Profile)]),
     "sixdgs_packed_weights_floats": (sz, []),
     "sixdgs_pack_weights": (i32, [vp] * 13 + [C.POINTER(ScorerWeights), vp]),
     "sixdgs_ray_encode": (i32, [vp, vp, vp, i64, vp, vp]),

@@ -114,3 +114,30 @@ def raster_views(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: t
     kw = dict(background=tuple(float(b) for b in background), scale_modifier=float(scale_modifier), scale_is_log=bool(scale_is_log),
               opacity_is_logit=bool(opacity_is_logit), max_instances=max_instances)
     return RasterViews.apply(xyz, scale, rot, opacity, f_dc, f_rest, cams, int(sh_degree), int(width), int(height), kw)
+
+
+class PhotometricLoss(torch.autograd.Function):
+    """loss [V] of ops.photometric_loss, differentiable in the image.  The forward asks the one C call for the gradient as well, with
+    grad_loss = 1; the backward scales it per view."""
+
+    @staticmethod
+    def forward(ctx, image, target, lambda_dssim: float):
+        if not ctx.needs_input_grad[0]:
+            return ops.photometric_loss(image, target, lambda_dssim=lambda_dssim)
+        loss, grad = ops.photometric_loss(image, target, lambda_dssim=lambda_dssim, want_grad=True)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (grad,) = ctx.saved_tensors
+        out = grad * grad_loss.to(grad.dtype).reshape(-1, 1, 1, 1)
+        if out.shape[3] == 4:
+            out[..., 3] = 0.0           # exact zero, as the C call writes it (0 x a negative grad_loss would be -0)
+        return out, None, None
+
+
+def photometric_loss(image: torch.Tensor, target: torch.Tensor, lambda_dssim: float = 0.2) -> torch.Tensor:
+    """(1 - lambda) L1 + lambda (1 - SSIM) per view [V] (sixdgs_photometric_loss in include/sixdgs.h), differentiable in image fp32
+    [V,H,W,3|4]; target fp32 [V,H,W,3|4] or uint8 [V,H,W,3], a constant."""
+    return PhotometricLoss.apply(image, target, float(lambda_dssim))

@@ -473,6 +473,66 @@ def raster_views_backward(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int
     return tuple(out.get(k) for k in RASTER_GRADIENTS)
 
 
+def photometric_loss_workspace_bytes(views: int, width: int, height: int, want_grad: bool = False) -> int:
+    return int(_lib.load().sixdgs_photometric_loss_workspace_bytes(int(views), int(width), int(height), int(bool(want_grad))))
+
+
+@_on_device
+def photometric_loss(image: torch.Tensor, target: torch.Tensor, *, lambda_dssim: float = 0.2, grad_loss: Optional[torch.Tensor] = None,
+                     want_grad: bool = False, want_parts: bool = False, workspace: Optional[torch.Tensor] = None,
+                     profile: Optional[Profile] = None):
+    """(1 - lambda) L1 + lambda (1 - SSIM) per view (sixdgs_photometric_loss in include/sixdgs.h defines it operation by operation).
+    image fp32 [V,H,W,3|4] (4: raster_views' float image; its fourth channel is not read); target fp32 [V,H,W,3|4] or uint8 [V,H,W,3]
+    (value u / 255); both contiguous and on one GPU.  Returns loss [V], then -- as far as asked for -- grad_image, the image's shape,
+    = grad_loss[v] d loss_v / d image (grad_loss [V], None: ones; want_grad), and parts [V,2] = (l1, ssim) (want_parts)."""
+    lam = float(lambda_dssim)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_dssim must be in [0, 1] (got {lambda_dssim})")
+    if not torch.is_tensor(image) or image.dim() != 4 or image.shape[3] not in (3, 4):
+        raise ValueError(f"image must be a [views,height,width,3|4] tensor (got {tuple(image.shape) if torch.is_tensor(image) else type(image).__name__})")
+    if image.dtype != torch.float32:
+        raise ValueError(f"image must be float32 (got {image.dtype})")
+    views, height, width, stride = image.shape
+    if not torch.is_tensor(target) or target.dim() != 4 or tuple(target.shape[:3]) != (views, height, width):
+        raise ValueError(f"target must be a [{views},{height},{width},3|4] tensor (got {tuple(target.shape) if torch.is_tensor(target) else type(target).__name__})")
+    if target.dtype == torch.uint8:
+        if target.shape[3] != 3:
+            raise ValueError("a uint8 target must have 3 channels")
+    elif target.dtype != torch.float32:
+        raise ValueError(f"target must be float32 or uint8 (got {target.dtype})")
+    elif target.shape[3] not in (3, 4):
+        raise ValueError("target must have 3 or 4 channels")
+    if width < 1 or height < 1:
+        raise ValueError(f"width and height must be positive (got {width} x {height})")
+    if not image.is_contiguous() or not target.is_contiguous():
+        raise ValueError("image and target must be contiguous")
+    if grad_loss is not None:
+        if not want_grad:
+            raise ValueError("grad_loss without want_grad")
+        if not torch.is_tensor(grad_loss) or tuple(grad_loss.shape) != (views,):
+            raise ValueError(f"grad_loss must be a [{views}] tensor")
+        grad_loss = _f32(grad_loss)
+    image, target = image.detach(), target.detach()
+    _need_gpu(image, target, grad_loss, workspace)
+    lib = _lib.load()
+    dev = image.device
+    need = lib.sixdgs_photometric_loss_workspace_bytes(views, width, height, int(want_grad))
+    if need == 0 and views > 0:
+        raise ValueError(f"sizes outside the photometric loss's limits (views {views}, {width} x {height})")
+    ws = workspace
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    loss = torch.empty(views, dtype=torch.float32, device=dev)
+    parts = torch.empty(views, 2, dtype=torch.float32, device=dev) if want_parts else None
+    grad = torch.empty_like(image) if want_grad else None
+    check(lib.sixdgs_photometric_loss(_p(image), stride, _p(target), int(target.dtype == torch.uint8), int(target.shape[3]), views, width,
+                                      height, lam, _p(grad_loss), _p(loss), _p(parts), _p(grad), _p(ws), ws.numel() * ws.element_size(),
+                                      _stream(), profile),
+          "photometric_loss")
+    out = [loss] + [o for o, want in ((grad, want_grad), (parts, want_parts)) if want]
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 # ---------------------------------------------------------------------------------------------
 # scorer
 # ---------------------------------------------------------------------------------------------

@@ -16,7 +16,10 @@ before writing the file.  Training, when no checkpoint exists, runs on rank 0 on
 Beyond the reference (keyword-only / extra flags, defaults reproduce it): --emitter / --max_ellipsoids / --rays_per_ellipsoid select
 full-scene emission (every Gaussian) instead of the reference's 1000-ellipsoid subsample; --skip_train evaluates random-init
 weights when no checkpoint exists (smoke runs); --n_iterations shortens training; --pose_solver consensus (with --inlier_scale and
---rays_to_output, up to 1024) solves the pose with the consensus solver (ops.solve_pose_consensus) instead of least squares.
+--rays_to_output, up to 1024) solves the pose with the consensus solver (ops.solve_pose_consensus) instead of least squares;
+--refine_steps N (with --refine_downscale, --refine_lr, --refine_lambda) refines every estimated pose by render-and-compare
+(refine.refine_results) on each rank's block and adds the refined_* and photometric_loss_* keys to its result dicts; the mean and
+median errors before and after go to <out_path>.refine_summary.json.  0, the default: no refinement, results.json as without the flag.
 """
 from __future__ import annotations
 
@@ -35,6 +38,7 @@ from .datasets import dotdict, get_checkpoint_arguments, load_data, parse_exp_di
 from .distance_based_loss import DistanceBasedScoreLoss
 from .identification_module import IdentificationModule
 from .sampling import generate_all_possible_rays
+from .refine import refine_results
 from .scene import GaussianScene
 from .test import test_pose_estimation
 from .train import train_id_module
@@ -72,7 +76,20 @@ def parse_args(argv=None):
                     help="carve the big per-scene buffers (key planes, select workspace, chain workspace) from ONE device buffer of this many GB allocated once "
                          "(ops.Arena) instead of asking the allocator scene by scene: a sweep over scenes of growing size otherwise pays a 100-200 GB hipMalloc "
                          "per scene.  -1: everything free but 56 GB; 0 (default): off")
+    ap.add_argument("--refine_steps", type=int, default=0,
+                    help="refine each estimated pose by render-and-compare for this many Adam steps (refine.refine_poses); 0 = off")
+    ap.add_argument("--refine_downscale", type=int, default=4, help="refinement compares at 1 / this of the query's resolution")
+    ap.add_argument("--refine_lr", type=float, default=2e-3, help="Adam step of the refinement")
+    ap.add_argument("--refine_lambda", type=float, default=0.2, help="weight of D-SSIM in the refinement's loss (the reference's lambda_dssim)")
     args, rest = ap.parse_known_args(argv)
+    if args.refine_steps < 0:
+        ap.error("--refine_steps must be >= 0 (0 = no refinement)")
+    if args.refine_downscale < 1:
+        ap.error("--refine_downscale must be >= 1")
+    if not args.refine_lr > 0:
+        ap.error("--refine_lr must be > 0")
+    if not 0.0 <= args.refine_lambda <= 1.0:
+        ap.error("--refine_lambda must be in [0, 1]")
     if args.data_parallel_train and not args.batched_window:
         ap.error("--data_parallel_train needs --batched_window")
     if args.backward_ray_groups < 0:
@@ -105,7 +122,8 @@ def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[s
                            starting_seed: int, lock_backbone: bool = True, device: str = "cuda", *, emission: Optional[dict] = None,
                            n_iterations: int = 1500, skip_train: bool = False, batch_size: int = 16, backbone: Optional[torch.nn.Module] = None,
                            batched_window: bool = False, data_parallel_train: bool = False, backward_ray_groups: int = 1,
-                           pose_solver: str = "ls", inlier_scale: Optional[float] = None, rays_to_output: int = 100):
+                           pose_solver: str = "ls", inlier_scale: Optional[float] = None, rays_to_output: int = 100,
+                           refine: Optional[dict] = None):
     """pretrain_eval_attention.py:31-160 for one scene; returns the result dicts of the inference pass for ALL test views (rank 0;
     other ranks return their own block).
 
@@ -116,7 +134,9 @@ def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[s
     distributed.init_from_env).  data_parallel_train: every rank takes part in the training (train_id_module(data_parallel=True)), inside
     the same stage; the ranks of a failing iteration leave it together.
 
-    pose_solver / inlier_scale / rays_to_output: handed to both passes of test_pose_estimation."""
+    pose_solver / inlier_scale / rays_to_output: handed to both passes of test_pose_estimation.  refine: the keyword arguments of
+    refine.refine_poses (steps, lr, lambda_dssim, downscale); when given, each rank refines the poses of its block after the inference
+    pass (refine.refine_results).  None: no refinement."""
     solver = dict(pose_solver=pose_solver, inlier_scale=inlier_scale, rays_to_output=rays_to_output)
     torch.manual_seed(starting_seed)
     print("data_path: ", checkpoint_args.source_path)
@@ -170,6 +190,12 @@ def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[s
         print("Testing performances on same points...")
         results, t_t, t_a, t_s, t_r = test_pose_estimation(mine, id_module, rays_ori, rays_dirs, rays_rgb, model_up, sequence_id=object_id,
                                                            category_id=category_name, save=False, save_all=False, batch_size=batch_size, **solver)
+        if refine:
+            print("Refining the estimated poses...")
+            try:
+                refine_results(gs_model, mine, results, **refine)
+            except RuntimeError:        # an optional post-pass: the unrefined rows stay (entries refined before the error keep their new keys)
+                traceback.print_exc()
         for r in results:
             r["frame_id"] += lo                  # frame ids count the scene's test views, not the rank's block
         print("Test AVG translation error: ", t_t)
@@ -187,6 +213,25 @@ def evaluate_single_object_in_blender(checkpoint_filepath: str, checkpoint_args,
     """pretrain_eval_attention.py:172-197."""
     return pretrain_single_object(checkpoint_filepath, checkpoint_args, exp_dir_filepath, object_id, category_name, starting_seed,
                                   device=device, lock_backbone=lock_backbone, **extras)
+
+
+def refine_summary(results: List[dict]) -> dict:
+    """Mean and median of the errors before and after refinement over the refined views, the unrefined ones from the same poses
+    (refine.pose_errors on pred_c2w), under key names of their own."""
+    from .refine import pose_errors
+
+    done = [r for r in results if "refined_c2w" in r]
+    out = {"refined_views": len(done), "views": len(results)}
+    if done:
+        t0, a0 = pose_errors(torch.tensor([r["gt_c2w"] for r in done]), torch.tensor([r["pred_c2w"] for r in done]))
+        cols = {"translation_error": t0.numpy(), "angular_error": a0.numpy(),
+                "refined_translation_error": np.array([r["refined_translation_error"] for r in done]),
+                "refined_angular_error": np.array([r["refined_angular_error"] for r in done]),
+                "photometric_loss_before": np.array([r["photometric_loss_before"] for r in done]),
+                "photometric_loss_after": np.array([r["photometric_loss_after"] for r in done])}
+        for k, v in cols.items():
+            out["mean_" + k], out["median_" + k] = float(np.nanmean(v)), float(np.nanmedian(v))
+    return out
 
 
 PREFIXES = {"blender": "synthetic_", "mip360": "mip_360_", "tankstemple": "tt_", "cambridge_landmark": "cl_"}
@@ -230,7 +275,9 @@ def main(argv=None, backbone: Optional[torch.nn.Module] = None) -> List[dict]:
                 n_iterations=args.n_iterations, skip_train=args.skip_train, batch_size=args.batch_size, backbone=backbone,
                 batched_window=args.batched_window, data_parallel_train=args.data_parallel_train,
                 backward_ray_groups=args.backward_ray_groups, pose_solver=args.pose_solver, inlier_scale=args.inlier_scale,
-                rays_to_output=args.rays_to_output)
+                rays_to_output=args.rays_to_output,
+                refine=dict(steps=args.refine_steps, lr=args.refine_lr, lambda_dssim=args.refine_lambda, downscale=args.refine_downscale)
+                if args.refine_steps > 0 else None)
             if rank == 0:
                 results.extend(obj)
         except RuntimeError:            # the only exception the reference survives per scene (pretrain_eval_attention.py:243-244)
@@ -242,6 +289,9 @@ def main(argv=None, backbone: Optional[torch.nn.Module] = None) -> List[dict]:
         print("Saving results")
         with open(out_path_abs, "w") as fh:
             json.dump(results, fh)
+        if args.refine_steps > 0:
+            with open(out_path_abs + ".refine_summary.json", "w") as fh:
+                json.dump(refine_summary(results), fh)
     dd.barrier()
     return results
 

@@ -277,6 +277,55 @@ int sixdgs_raster_views_backward(const float* xyz, const float* scale, int scale
                                  void* ws, size_t ws_bytes, sixdgs_stream_t stream, sixdgs_profile* prof);
 
 /* ---------------------------------------------------------------------------------------------
+ * The photometric loss of render-and-compare (additive in ABI 10): per view loss_v = (1 - lambda) L1 + lambda (1 - SSIM) between an
+ * image a and a target b, and grad_image = grad_loss[v] d loss_v / d a.  It is the reference's training objective (train.py:119 with
+ * lambda_dssim = 0.2; utils/loss_utils.py: 11 x 11 Gaussian window, sigma 1.5, padding 5, one group per channel).  All arithmetic in
+ * fp32, no contraction into fused multiply-adds.  Per view v and channel c in {r, g, b}:
+ *   1. a = image[v][y][x][c], image fp32 [views][height][width][image_stride], image_stride 3 or 4 (4: sixdgs_raster_views' image_f32;
+ *      the fourth channel is never read);
+ *   2. b = target[v][y][x][c]: fp32 [views][height][width][target_stride], target_stride 3 or 4 (target_is_u8 == 0), or uint8
+ *      [views][height][width][3] with b = float(u) / 255.0f (target_is_u8 == 1, target_stride 3);
+ *   3. w[11] = SIXDGS_SSIM_WINDOW below: the fp32 roundings of exp(-(i - 5)^2 / 4.5) / sum, normalised in fp64;
+ *   4. blur(f)(x, y) = sum_j w[j] h(x, y + j - 5), h(x, y) = sum_k w[k] f(x + k - 5, y): first along x, then along y, each sum
+ *      started with its term 0 and continued in ascending index; f counts as ZERO outside the image, h is formed from that;
+ *   5. mu1 = blur(a), mu2 = blur(b), s1 = blur(a a) - mu1 mu1, s2 = blur(b b) - mu2 mu2, s12 = blur(a b) - mu1 mu2;
+ *   6. A1 = 2 (mu1 mu2) + C1, A2 = 2 s12 + C2, B1 = (mu1 mu1 + mu2 mu2) + C1, B2 = (s1 + s2) + C2, C1 = 1e-4f, C2 = 9e-4f;
+ *      m = (A1 A2) / (B1 B2);
+ *   7. per pixel the channels are added r, g, b: (m_r + m_g) + m_b and likewise |a - b|.  The pixels of a 16 x 16 tile (the
+ *      rasteriser's grid gx = ceil(width / 16), gy = ceil(height / 16); pixels outside the image count as 0) are added in a fixed tree:
+ *      the 256 pixels in 4 groups of 64 in rows-of-16 order, within a group x += x_(l xor s), s = 32 .. 1, then the groups in order;
+ *      then the tiles of the view in row-major order, one after the other.  With n = float(3 height width):
+ *      l1_v = sum |a - b| / n, ssim_v = sum m / n, loss_v = (1 - lambda) l1_v + lambda (1 - ssim_v).
+ * The gradient is the standard two-pass one.  With blur(a a) and blur(a b) held, per pixel and channel
+ *   d_s1 = -(m / B2),  d_s12 = (2 A1) / (B1 B2),
+ *   d_mu1 = (((2 mu2) A2) / (B1 B2) - ((2 mu1) m) / B1) - ((2 mu1) d_s1 + mu2 d_s12)
+ * are the derivatives of m by s1, s12 and mu1 (the last one total: through B1, A1 and through s1, s12).  These three maps are stored;
+ * the window is symmetric, so the same blur with the same zero rule is the adjoint, and
+ *   X = (blur(d_mu1) + (2 a) blur(d_s1)) + b blur(d_s12),
+ *   grad_image[v][y][x][c] = g_v (((1 - lambda) / n) sign(a - b) - (lambda / n) X),  sign(0) = 0, g_v = grad_loss[v] (NULL: 1).
+ * With image_stride 4 the fourth channel of grad_image is written as exact zero.
+ *
+ * Outputs, each may be NULL, WRITTEN, NOT ACCUMULATED: loss [views]; parts [views][2] = (l1_v, ssim_v); grad_image, the image's shape.
+ * With grad_image NULL neither the maps nor the second pass run and the smaller workspace suffices; with all three NULL nothing runs.
+ * SAME INPUT, SAME BYTES on every call: no floating-point atomics.  VIEWS DO NOT MIX: loss[v], parts[v] and grad_image[v] are the
+ * same bits whether view v is passed alone or in a batch.  Nothing is read outside the arrays as declared, and the fourth channel of a
+ * stride-4 image or target is not read at all.  image, target (fp32), grad_loss and the outputs are 4-byte aligned, ws 256-byte.
+ * Limits: 1 <= width, height <= 16384, views <= 65535, views gx gy < 2^31, lambda in [0, 1] (so finite).  Argument errors:
+ * SIXDGS_E_BADARG; too small a workspace: SIXDGS_E_WORKSPACE; both without touching a GPU.  views == 0 returns 0.
+ * sixdgs_photometric_loss_workspace_bytes is answered without a GPU and is 0 outside the limits: 8 B per tile and view, plus, with
+ * want_grad, 36 B per pixel and view (the three maps of three channels, planar).  prof (may be NULL) receives one slot per stage:
+ * moments (steps 1 - 6 and the tile sums), sums (step 7; only with loss or parts), gradient (only with grad_image). */
+#define SIXDGS_SSIM_WINDOW                                                                                              \
+  {0.00102838012f, 0.00759875821f, 0.0360007733f, 0.109360687f, 0.213005543f, 0.266011715f, 0.213005543f, 0.109360687f, \
+   0.0360007733f,  0.00759875821f, 0.00102838012f}
+size_t sixdgs_photometric_loss_workspace_bytes(int views, int width, int height, int want_grad);
+int sixdgs_photometric_loss(const float* image /*[views][height][width][image_stride]*/, int image_stride /*3 or 4*/,
+                            const void* target, int target_is_u8, int target_stride /*3 or 4; 3 with uint8*/, int views, int width,
+                            int height, float lambda, const float* grad_loss /*[views] device or NULL*/, float* loss /*[views]*/,
+                            float* parts /*[views][2]*/, float* grad_image, void* ws, size_t ws_bytes, sixdgs_stream_t stream,
+                            sixdgs_profile* prof);
+
+/* ---------------------------------------------------------------------------------------------
  * Scorer, scene side (once per scene): ray MLP + k_proj -> key cache
  * replaces RayPreprocessor.forward (ray_preprocessor.py:36-46) + k_proj (our_multihead_attention.py:74)
  * ------------------------------------------------------------------------------------------- */

@@ -1,13 +1,15 @@
 """Two short demonstrations of the rasteriser's gradients (autograd.raster_views): Adam on an L1 photometric loss against views
 rendered from the true state of make_scene.
 
-    python tools/raster_fit.py [--gaussians 20000] [--size 128] [--steps 200] [--views 4]
+    python tools/raster_fit.py [--gaussians 20000] [--size 128] [--steps 200] [--views 4] [--loss l1|dssim]
 
   (a) pose      one camera perturbed by a small translation and rotation; a 6-vector (translation, axis-angle) composed onto the
                 perturbed w2c row in torch is optimised, the scene is fixed.  Error: translation (scene units) and rotation (degrees)
                 of the composed camera against the true one.
   (b) colours   the scene's f_dc and opacities perturbed; they are optimised against `views` fixed cameras.  Error: RMS of f_dc and
                 of the opacity logits against the true ones.
+--loss dssim runs (a) on autograd.photometric_loss, (1 - 0.2) L1 + 0.2 (1 - SSIM), instead of the L1 composed in torch (the default,
+which profiles/raster_backward.md recorded).  rodrigues and compose live in 6dgs_amd/refine.py, which batches (a) as refine_poses.
 Prints loss and parameter error every 10 steps.  No thresholds: a demonstration (profiles/raster_backward.md keeps its output)."""
 import argparse
 import importlib
@@ -24,22 +26,6 @@ if ROOT not in sys.path:
 BACKGROUND = (1.0, 1.0, 1.0)
 
 
-def rodrigues(w):
-    """Rotation matrix of the axis-angle vector w [3] (differentiable, fine at w = 0)."""
-    th2 = (w * w).sum()
-    th = torch.sqrt(th2 + 1e-20)
-    zero = torch.zeros((), device=w.device)
-    K = torch.stack([torch.stack([zero, -w[2], w[1]]), torch.stack([w[2], zero, -w[0]]), torch.stack([-w[1], w[0], zero])])
-    return torch.eye(3, device=w.device) + (torch.sin(th) / th) * K + ((1 - torch.cos(th)) / (th2 + 1e-20)) * (K @ K)
-
-
-def compose(row, delta):
-    """The camera row [16] with the rigid motion delta = (translation, axis-angle) applied after its w2c: [dR R | dR t + dt]."""
-    m = row[:12].reshape(3, 4)
-    dR = rodrigues(delta[3:])
-    return torch.cat([torch.cat([dR @ m[:, :3], (dR @ m[:, 3] + delta[:3])[:, None]], dim=1).reshape(-1), row[12:]])
-
-
 def pose_error(row, true):
     a, b = row[:12].reshape(3, 4).detach().double(), true[:12].reshape(3, 4).double()
     ca, cb = -a[:, :3].T @ a[:, 3], -b[:, :3].T @ b[:, 3]                   # camera centres
@@ -53,9 +39,11 @@ def main():
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--views", type=int, default=4)
+    ap.add_argument("--loss", choices=["l1", "dssim"], default="l1", help="(a): L1 composed in torch, or the fused L1 + D-SSIM loss")
     args = ap.parse_args()
     syn, ops = importlib.import_module("6dgs_amd.synthetic"), importlib.import_module("6dgs_amd.ops")
     autograd, render = importlib.import_module("6dgs_amd.autograd"), importlib.import_module("6dgs_amd.render")
+    compose = importlib.import_module("6dgs_amd.refine").compose
     sc = syn.make_scene(args.gaussians, 0)
     scene = [torch.from_numpy(np.ascontiguousarray(sc[k])).cuda() for k in ("xyz", "log_scale", "rot", "opacity", "f_dc", "f_rest")]
     rows = torch.from_numpy(render.camera_rows(syn.make_cameras(args.views, 21, width=args.size, height=args.size))).cuda()
@@ -70,10 +58,13 @@ def main():
     for step in range(args.steps + 1):
         row = compose(start, delta)
         image = autograd.raster_views(*scene, 3, row[None], *size, background=BACKGROUND)
-        loss = (image[..., :3] - target[:1, ..., :3]).abs().mean()
+        if args.loss == "dssim":
+            loss = autograd.photometric_loss(image, target[:1], 0.2).sum()
+        else:
+            loss = (image[..., :3] - target[:1, ..., :3]).abs().mean()
         if step % 10 == 0:
             terr, rerr = pose_error(row, rows[0])
-            print(f"  step {step:4d}: L1 {float(loss.detach()):.5f}, centre error {terr:.5f}, rotation error {rerr:.4f} deg")
+            print(f"  step {step:4d}: {'L1' if args.loss == 'l1' else 'L1 + D-SSIM'} {float(loss.detach()):.5f}, centre error {terr:.5f}, rotation error {rerr:.4f} deg")
         opt.zero_grad()
         loss.backward()
         opt.step()
