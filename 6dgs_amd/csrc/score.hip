@@ -1101,6 +1101,59 @@ __global__ void __launch_bounds__(256) k_split_tiles_f16(const float* __restrict
   }
 }
 
+// The same split for the q of the two-pass scorer: one block per (image, 128-token half) of q [nb][256][384], dst [nb][256][1536 B],
+// inv_scale [nb][2].  Rows at or beyond the image's token count are NOT READ: they are written as zero planes and take no part in the
+// half's scale (k_split_q_slots does the same per quarter) -- whatever the caller left there, a huge value, an Inf or a NaN, cannot push
+// the real rows into fp16's subnormals.  A half without tokens: scale 1, zero planes.
+__global__ void __launch_bounds__(256) k_split_q_tiles_f16(const float* __restrict__ q, const int* __restrict__ n_tok, char* __restrict__ dst,
+                                                           float* __restrict__ inv_scale) {
+  __shared__ float wmax[4];
+  const int bl = blockIdx.x >> 1, half = blockIdx.x & 1;
+  const int n = min(128, max(0, n_tok[bl] - 128 * half));
+  const float* base = q + ((int64_t)bl * kT + 128 * half) * SIXDGS_D;
+  float m = 0.f;
+  for (int i = threadIdx.x; i < n * 96; i += 256) {
+    const float4 v = *reinterpret_cast<const float4*>(base + (int64_t)i * 4);
+    m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));   // NaN operands are skipped by fmaxf
+  }
+  m = sdg_wave_max(m);
+  if (sdg_lane() == 0) wmax[sdg_wave()] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+  int sh = 0;
+  if (m > 0.f && m < INFINITY) {
+    int e;
+    frexpf(m, &e);
+    sh = 14 - e;
+    sh = sh > 100 ? 100 : (sh < -100 ? -100 : sh);
+  }
+  const float sc = ldexpf(1.f, sh);
+  if (threadIdx.x == 0) inv_scale[blockIdx.x] = ldexpf(1.f, -sh);
+  char* const drow = dst + ((int64_t)bl * kT + 128 * half) * kRowF;
+  for (int i = threadIdx.x; i < 128 * 48; i += 256) {
+    const int row = i / 48, k8 = i - row * 48;
+    f16x8 h, l;
+    if (row < n) {
+      const float* sp = base + (int64_t)row * SIXDGS_D + k8 * 8;
+      const float4 lo = *reinterpret_cast<const float4*>(sp);
+      const float4 hi = *reinterpret_cast<const float4*>(sp + 4);
+      const float x[8] = {lo.x * sc, lo.y * sc, lo.z * sc, lo.w * sc, hi.x * sc, hi.y * sc, hi.z * sc, hi.w * sc};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const _Float16 hh = (_Float16)x[e];
+        h[e] = hh;
+        l[e] = (_Float16)(x[e] - (float)hh);
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) h[e] = l[e] = (_Float16)0.f;
+    }
+    char* d = drow + (int64_t)row * kRowF + (k8 >> 2) * kSlabF + (k8 & 3) * 16;
+    *reinterpret_cast<f16x8*>(d) = h;
+    *reinterpret_cast<f16x8*>(d + 64) = l;
+  }
+}
+
 
 // merge the per-group partial statistics: stats[b][t] = (max, sumexp).  Four threads per token take every fourth group
 // (independent load chains), then one thread folds the four partials in a fixed order.
@@ -2234,10 +2287,10 @@ int score_impl(int phase, bool planes, const float* q, const int32_t* d_n_tok, c
                               use_f16 ? (double)r * (kRowF + tok * (logits24 ? 3.0 + 8.0 / 128.0 : 4.0))
                                       : (double)r * (nb * (SIXDGS_D * 4.0) + tok * 4.0));
         if (use_f16) {
-          // scaled fp16 planes of q (one power-of-two scale per 128-token half), then the fp16x3 kernel
+          // scaled fp16 planes of q (one power-of-two scale per 128-token half, taken over the rows below the token count), then the fp16x3 kernel
           float* qinv = (float*)(qplanes + (size_t)bg * (p.per_image_qplanes - 256));
-          hipLaunchKernelGGL(k_split_tiles_f16, dim3((unsigned)(2 * nb)), dim3(256), 0, s, q + (int64_t)b0 * kT * SIXDGS_D,
-                             (int64_t)nb * kT, (int64_t)SIXDGS_D, qplanes, qinv);
+          hipLaunchKernelGGL(k_split_q_tiles_f16, dim3((unsigned)(2 * nb)), dim3(256), 0, s, q + (int64_t)b0 * kT * SIXDGS_D, d_n_tok + b0,
+                             qplanes, qinv);
           LogitsF16Args V = {qplanes - (int64_t)b0 * kT * kRowF, d_n_tok, (const char*)key_planes, qinv - 2 * b0, d_key_scale, logits,
                              partial, r, A.ldl, p.tiles_per_group, p.n_tiles, p.n_groups, b0, nb};
           // 256-ray tiles in groups: the group count is a multiple of the CU count (equal-length runs, no partial last

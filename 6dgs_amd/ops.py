@@ -967,7 +967,9 @@ def score_topk(q: torch.Tensor, n_tok: torch.Tensor, key: Optional[torch.Tensor]
                profile: Optional["KernelProfile"] = None, n_tok_host=None, key_planes: Optional[torch.Tensor] = None,
                key_scale: Optional[torch.Tensor] = None):
     """key: fp32 [R,384] and/or key_planes: uint8 [R,1536] scaled fp16 planes + key_scale (the F16X3 modes: the DMA-fed kernels);
-    MMA_F32 / MMA_BF16X6 score on the fp32 keys."""
+    MMA_F32 / MMA_BF16X6 score on the fp32 keys.  q fp32 [B,256,384]: rows at or beyond n_tok[b] are not read in any mode (they may hold
+    anything, NaN and Inf included); stats rows there are unspecified.  Returns (idx [B,k], val [B,k], scores [B,R] | None, stats [B,256,2] | None);
+    idx / val beyond min(R, k) are (-1, NaN)."""
     q = _f32(q)
     key = _f32(key) if key is not None else None
     _need_gpu(q, key, n_tok, key_planes)

@@ -60,7 +60,12 @@ typedef void* sixdgs_stream_t;
 /*   F16X3_L32  as F16X3, but the logits travel between the two scorer passes as fp32 (1 KiB per ray and image).  F16X3
  *           stores them as 24-bit fixed point of (lane maximum - logit), resolution 2^-19 (absolute error <= 2^-20 per logit,
  *           the fp32 rounding of a logit of magnitude 16; measured effect on the scores <= 5e-7 relative): 768 B per ray and
- *           image through HBM twice, the largest data stream of the path. */
+ *           image through HBM twice, the largest data stream of the path.  The grid ends at 2^24 - 1 steps: a logit more than
+ *           32 below the lane maximum (the largest logit of that token among the lane's 64 rays of the 128-ray tile) is stored
+ *           as that maximum minus 32.  The score of such a ray is therefore too LARGE, never too small: by at most
+ *           e^-32 * sum_t max_{r' in the 128-ray tile of r} softmax_r'(token t), i.e. e^-32 of the tile's largest term per token.
+ *           Such rays carry no weight in the pose; with a single token and a logit spread beyond 32 the ORDER among rays of that
+ *           size can differ from F16X3_L32's (tests/test_gpu_two_pass_edges.py: test_clamp). */
 #define SIXDGS_MMA_F16X3_L32 3
 
 /* Optional kernel timing, owned by the caller (the library stays stateless): zero-initialise, pass to
@@ -463,8 +468,11 @@ int sixdgs_image_prep(const uint8_t* images, int batch, int height, int width, c
 int sixdgs_q_proj(const float* tokens, const int32_t* d_n_tok, int batch,
                   const sixdgs_scorer_weights* w, float* q, sixdgs_stream_t stream);
 
-/* scores[b][r] = sum_t softmax_r(q[b][t] . key[r] / sqrt(384)); idx/val = top-k (sorted
+/* scores[b][r] = sum_{t < n_tok[b]} softmax_r(q[b][t] . key[r] / sqrt(384)); idx/val = top-k (sorted
  * descending, ties -> lowest index).  scores may be NULL (then they live only in the workspace).
+ * q rows at or beyond n_tok[b] are NOT READ, in any mode and by every entry point of the scorer (sixdgs_score_topk[_ex],
+ * sixdgs_score_pass1): they may hold anything -- NaN, Inf, values of any magnitude -- without changing a bit of the scores, the
+ * top-k or the row statistics of the rows below n_tok[b] (row_stats rows at or beyond n_tok[b] are unspecified).
  * Never materialises more than `ws` allows: images are processed in groups that fit. */
 size_t sixdgs_score_topk_workspace_bytes(int64_t r, int batch, int topk);   /* enough for every mode */
 /* exact for a mode: with key planes in F16X3 / DEFAULT the logits take 784 instead of 1024 B per ray and image */
