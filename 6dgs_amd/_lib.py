@@ -61,6 +61,11 @@ SIGNATURES = {
                                            vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Profile)]),
     "sixdgs_photometric_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "sixdgs_photometric_loss": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Profile)]),
+    "sixdgs_pose_compose": (i32, [vp, vp, i32, vp, vp]),
+    "sixdgs_pose_step": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float] + [vp] * 10 + [vp]),
+    "sixdgs_refine_poses_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
+    "sixdgs_refine_poses": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, i32, i32, C.c_float, vp, vp, i32, i32, C.c_float,
+                                  i32, C.c_float, C.c_float, C.c_float, C.c_float, i64] + [vp] * 7 + [vp, sz, vp]),
     "sixdgs_packed_weights_floats": (sz, []),
     "sixdgs_pack_weights": (i32, [vp] * 13 + [C.POINTER(ScorerWeights), vp]),
     "sixdgs_ray_encode": (i32, [vp, vp, vp, i64, vp, vp]),

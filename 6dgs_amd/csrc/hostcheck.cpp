@@ -1,5 +1,5 @@
-// hostcheck.cpp -- HOST instantiation of device_math.h (the per-thread math of the HIP kernels) and of dense_layout.h (the index
-// arithmetic of the ray-MLP chain's operand planes) behind
+// hostcheck.cpp -- HOST instantiation of device_math.h (the per-thread math of the HIP kernels), of dense_layout.h (the index
+// arithmetic of the ray-MLP chain's operand planes) and of pose_step.h (the per-view arithmetic of pose refinement) behind
 // a tiny C ABI, so the CPU test-suite can compare the product's arithmetic with the oracle and the
 // golden vectors without a GPU.  Contains no kernels; never used by the product path.
 #include <stdlib.h>
@@ -8,6 +8,7 @@
 #include "sweep_plan.h"
 #include "dense_layout.h"
 #include "sweep_layout.h"
+#include "pose_step.h"
 using namespace sdg;
 
 extern "C" {
@@ -177,6 +178,31 @@ int hc_sw_out_index(int lane, int x) { return sw::out_index(lane, x); }
 int hc_sw_out_ray(int lane, int x) { return sw::out_ray(lane, x); }
 int hc_sw_part_writes(int lane) { return sw::part_writes(lane) ? 1 : 0; }
 int hc_sw_part_row(int wn, int lane) { return sw::part_row(wn, lane); }
+// ---- pose_step.h: the per-view arithmetic of refine.hip (tests/test_pose_step_host.py) ----
+float hc_ps_series_below() { return ps::kSeriesBelow; }
+void hc_ps_coeffs(const float* x, long long n, float* abc) {
+  for (long long i = 0; i < n; ++i) {
+    const ps::Coeffs k = ps::rot_coeffs(x[i]);
+    abc[3 * i] = k.a; abc[3 * i + 1] = k.b; abc[3 * i + 2] = k.c;
+  }
+}
+void hc_ps_compose(const float* start, const float* delta, long long views, float* rows) {
+  for (long long v = 0; v < views; ++v) ps::compose(start + 16 * v, delta + 6 * v, rows + 16 * v);
+}
+void hc_ps_chain(const float* start, const float* delta, const float* d_rows, long long views, float* g) {
+  for (long long v = 0; v < views; ++v) ps::chain(start + 16 * v, delta + 6 * v, d_rows + 16 * v, g + 6 * v);
+}
+// sixdgs_pose_step on the host: the same per-view function in the kernel's order (view 0 owns instances_needed)
+void hc_ps_step(const float* start, const float* loss, const float* d_rows, const long long* instances, long long max_instances, int views, int step,
+                int evaluate_only, float lr, float beta1, float beta2, float eps, float* delta, float* m, float* v, float* rows, float* best_loss,
+                int* best_step, float* best_rows, float* history_row, int* status, long long* instances_needed) {
+  const ps::Adam p = ps::adam_at(step, lr, beta1, beta2, eps);
+  const long long count = instances ? *instances : 0;
+  if (views > 0 && count > *instances_needed) *instances_needed = count;
+  for (int i = 0; i < views; ++i)
+    ps::step_view(start + 16 * i, d_rows ? d_rows + 16 * i : nullptr, loss[i], count, max_instances, step, evaluate_only != 0, p, delta + 6 * i,
+                  m + 6 * i, v + 6 * i, rows + 16 * i, best_loss + i, best_step + i, best_rows + 16 * i, history_row + i, status + i);
+}
 int hc_dl_const(int which) {
   const int v[] = {dl::kSlabB, dl::kPRow, dl::kGran, dl::kGranSlab, dl::kChunkRun};
   return which >= 0 && which < 5 ? v[which] : -1;

@@ -1,0 +1,208 @@
+// refine.hip -- render-and-compare pose refinement below the C ABI (include/sixdgs.h: sixdgs_pose_compose, sixdgs_pose_step,
+// sixdgs_refine_poses).  The pose arithmetic is pose_step.h's, one thread per view, one owner per output, no atomics; the loop
+// enqueues the rasteriser, the photometric loss, the rasteriser's backward and the pose step on one stream through their own entry
+// points and never reads anything back.
+#include <math.h>
+
+#include "common.h"
+#include "pose_step.h"
+
+namespace {
+
+using namespace sdg;
+
+constexpr int kBlock = 64;
+constexpr int kMaxViews = 65535;
+
+struct StepArgs {
+  const float* start;
+  const float* loss;
+  const float* d_rows;
+  const int64_t* instances;
+  int64_t max_instances;
+  int views, step, evaluate_only;
+  ps::Adam adam;
+  float *delta, *m, *v, *rows, *best_loss;
+  int32_t* best_step;
+  float *best_rows, *history;
+  int32_t* status;
+  int64_t* instances_needed;
+};
+
+__global__ __launch_bounds__(kBlock) void k_pose_compose(const float* __restrict__ start, const float* __restrict__ delta, int views,
+                                                         float* __restrict__ rows) {
+  const int v = blockIdx.x * kBlock + threadIdx.x;
+  if (v >= views) return;
+  ps::compose(start + 16 * (size_t)v, delta + 6 * (size_t)v, rows + 16 * (size_t)v);
+}
+
+// the state sixdgs_refine_poses starts from: delta = m = v = 0, iterate 0, nothing seen yet
+__global__ __launch_bounds__(kBlock) void k_pose_init(const float* __restrict__ start, int views, float* delta, float* m, float* vv, float* rows,
+                                                      float* best_loss, int32_t* best_step, float* best_rows, int32_t* status,
+                                                      int64_t* instances_needed) {
+  const int v = blockIdx.x * kBlock + threadIdx.x;
+  if (v >= views) return;
+  for (int i = 0; i < 6; ++i) delta[6 * (size_t)v + i] = m[6 * (size_t)v + i] = vv[6 * (size_t)v + i] = 0.f;
+  ps::compose(start + 16 * (size_t)v, delta + 6 * (size_t)v, rows + 16 * (size_t)v);
+  for (int j = 0; j < 16; ++j) best_rows[16 * (size_t)v + j] = start[16 * (size_t)v + j];
+  best_loss[v] = INFINITY;
+  best_step[v] = 0;
+  status[v] = 0;
+  if (v == 0) *instances_needed = 0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_pose_step(StepArgs A) {
+  const int v = blockIdx.x * kBlock + threadIdx.x;
+  if (v >= A.views) return;
+  const int64_t count = A.instances ? *A.instances : 0;
+  if (v == 0 && count > *A.instances_needed) *A.instances_needed = count;
+  const size_t r = 16 * (size_t)v, d = 6 * (size_t)v;
+  ps::step_view(A.start + r, A.d_rows ? A.d_rows + r : nullptr, A.loss[v], count, A.max_instances, A.step, A.evaluate_only != 0, A.adam,
+                A.delta + d, A.m + d, A.v + d, A.rows + r, A.best_loss + v, A.best_step + v, A.best_rows + r, A.history + v, A.status + v);
+}
+
+bool adam_ok(float lr, float beta1, float beta2, float eps) {
+  return lr > 0.f && lr < INFINITY && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && eps < INFINITY;
+}
+
+bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
+int launch_step(const StepArgs& A, hipStream_t s) {
+  hipLaunchKernelGGL(k_pose_step, dim3((unsigned)sdg_cdiv(A.views, kBlock)), dim3(kBlock), 0, s, A);
+  SDG_LAUNCH_OK();
+  return 0;
+}
+
+struct Layout {
+  size_t fwd, bwd, photo, image, grad, rows, d_rows, loss, delta, m, v, count, total;
+  size_t fwd_bytes, bwd_bytes, photo_bytes;
+};
+
+// 0 total = outside the limits (the rasteriser's: its workspace is never 0 inside them)
+Layout layout(int64_t n, int views, int width, int height, int64_t max_instances) {
+  Layout L = {};
+  L.fwd_bytes = sixdgs_raster_views_workspace_bytes(n, views, width, height, max_instances);
+  L.bwd_bytes = sixdgs_raster_views_backward_workspace_bytes(n, views, width, height, max_instances);
+  if (L.fwd_bytes == 0 || L.bwd_bytes == 0) return L;
+  L.photo_bytes = sixdgs_photometric_loss_workspace_bytes(views, width, height, 1);
+  if (views > 0 && L.photo_bytes == 0) return L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t at = o; o += sdg_align(bytes); return at; };
+  const size_t px = (size_t)views * (size_t)height * (size_t)width, nv = (size_t)views;
+  L.fwd = take(L.fwd_bytes);
+  L.bwd = take(L.bwd_bytes);
+  L.photo = take(L.photo_bytes);
+  L.image = take(px * 4 * sizeof(float));
+  L.grad = take(px * 4 * sizeof(float));
+  L.rows = take(nv * 16 * sizeof(float));
+  L.d_rows = take(nv * 16 * sizeof(float));
+  L.loss = take(nv * sizeof(float));
+  L.delta = take(nv * 6 * sizeof(float));
+  L.m = take(nv * 6 * sizeof(float));
+  L.v = take(nv * 6 * sizeof(float));
+  L.count = take(sizeof(int64_t));
+  L.total = o;
+  return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sixdgs_pose_compose(const float* start, const float* delta, int views, float* rows, sixdgs_stream_t stream) {
+  SDG_CHECK_ARG(views >= 0 && views <= kMaxViews);
+  if (views == 0) return 0;
+  SDG_CHECK_ARG(start && delta && rows && rows != start);
+  SDG_CHECK_ARG(aligned4(start) && aligned4(delta) && aligned4(rows));
+  hipLaunchKernelGGL(k_pose_compose, dim3((unsigned)sdg_cdiv(views, kBlock)), dim3(kBlock), 0, sdg_stream(stream), start, delta, views, rows);
+  SDG_LAUNCH_OK();
+  return 0;
+}
+
+int sixdgs_pose_step(const float* start, const float* loss, const float* d_rows, const int64_t* instances, int64_t max_instances, int views,
+                     int step, int evaluate_only, float lr, float beta1, float beta2, float eps, float* delta, float* m, float* v, float* rows,
+                     float* best_loss, int32_t* best_step, float* best_rows, float* history_row, int32_t* status, int64_t* instances_needed,
+                     sixdgs_stream_t stream) {
+  SDG_CHECK_ARG(views >= 0 && views <= kMaxViews);
+  SDG_CHECK_ARG(step >= 0 && step < INT32_MAX && (evaluate_only == 0 || evaluate_only == 1));
+  SDG_CHECK_ARG(max_instances >= 1 && max_instances < ((int64_t)1 << 31));
+  SDG_CHECK_ARG(adam_ok(lr, beta1, beta2, eps));
+  if (views == 0) return 0;
+  SDG_CHECK_ARG(start && loss && (evaluate_only || d_rows) && delta && m && v && rows && best_loss && best_step && best_rows && history_row &&
+                status && instances_needed);
+  SDG_CHECK_ARG(rows != start && best_rows != rows);
+  SDG_CHECK_ARG(aligned4(start) && aligned4(loss) && aligned4(d_rows) && aligned4(delta) && aligned4(m) && aligned4(v) && aligned4(rows) &&
+                aligned4(best_loss) && aligned4(best_step) && aligned4(best_rows) && aligned4(history_row) && aligned4(status));
+  SDG_CHECK_ARG(((uintptr_t)instances & 7) == 0 && ((uintptr_t)instances_needed & 7) == 0);
+  const StepArgs A = {start, loss,      evaluate_only ? nullptr : d_rows, instances, max_instances, views,   step,  evaluate_only,
+                      ps::adam_at(step, lr, beta1, beta2, eps), delta, m, v, rows, best_loss, best_step, best_rows, history_row, status,
+                      instances_needed};
+  return launch_step(A, sdg_stream(stream));
+}
+
+size_t sixdgs_refine_poses_workspace_bytes(int64_t n, int views, int width, int height, int64_t max_instances) {
+  return layout(n, views, width, height, max_instances).total;
+}
+
+int sixdgs_refine_poses(const float* xyz, const float* scale, int scale_is_log, const float* rot, const float* opacity, int opacity_is_logit,
+                        const float* f_dc, const float* f_rest, int sh_degree, int n_coef, int64_t n, const float* start_rows, int views,
+                        int width, int height, float scale_modifier, const float* background, const void* target, int target_is_u8,
+                        int target_stride, float lambda, int steps, float lr, float beta1, float beta2, float eps, int64_t max_instances,
+                        float* best_rows, float* best_loss, int32_t* best_step, float* history, float* delta, int32_t* status,
+                        int64_t* instances_needed, void* ws, size_t ws_bytes, sixdgs_stream_t stream) {
+  const Layout L = layout(n, views, width, height, max_instances);
+  SDG_CHECK_ARG(L.total != 0);
+  SDG_CHECK_ARG(scale_modifier > 0.f && scale_modifier < INFINITY);
+  SDG_CHECK_ARG(sh_degree >= 0 && sh_degree <= 3 && n_coef >= (sh_degree + 1) * (sh_degree + 1) && n_coef <= 16);
+  SDG_CHECK_ARG(target_is_u8 == 0 || target_is_u8 == 1);
+  SDG_CHECK_ARG(target_is_u8 ? target_stride == 3 : (target_stride == 3 || target_stride == 4));
+  SDG_CHECK_ARG(lambda >= 0.f && lambda <= 1.f);
+  SDG_CHECK_ARG(steps >= 1 && steps < INT32_MAX - 1);
+  SDG_CHECK_ARG(adam_ok(lr, beta1, beta2, eps));
+  if (views == 0) return 0;
+  SDG_CHECK_ARG(start_rows && background && target);
+  SDG_CHECK_ARG(n == 0 || (xyz && scale && rot && opacity && f_dc && (n_coef == 1 || f_rest)));
+  SDG_CHECK_ARG(best_rows && best_loss && best_step && history && status && instances_needed);
+  SDG_CHECK_ARG(aligned4(start_rows) && (target_is_u8 || aligned4(target)) && aligned4(best_rows) && aligned4(best_loss) && aligned4(best_step) &&
+                aligned4(history) && aligned4(delta) && aligned4(status) && ((uintptr_t)instances_needed & 7) == 0);
+  if (ws_bytes < L.total) return SIXDGS_E_WORKSPACE;
+  SDG_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0);
+  hipStream_t s = sdg_stream(stream);
+  char* w = (char*)ws;
+  float* image = (float*)(w + L.image);
+  float* grad = (float*)(w + L.grad);
+  float* rows = (float*)(w + L.rows);
+  float* d_rows = (float*)(w + L.d_rows);
+  float* loss = (float*)(w + L.loss);
+  float* dl = delta ? delta : (float*)(w + L.delta);
+  float* m = (float*)(w + L.m);
+  float* v = (float*)(w + L.v);
+  int64_t* count = (int64_t*)(w + L.count);
+  hipLaunchKernelGGL(k_pose_init, dim3((unsigned)sdg_cdiv(views, kBlock)), dim3(kBlock), 0, s, start_rows, views, dl, m, v, rows, best_loss,
+                     best_step, best_rows, status, instances_needed);
+  SDG_LAUNCH_OK();
+  for (int step = 0; step <= steps; ++step) {
+    const int last = step == steps;
+    int st = sixdgs_raster_views(xyz, scale, scale_is_log, rot, opacity, opacity_is_logit, f_dc, f_rest, sh_degree, n_coef, n, rows, views,
+                                 width, height, scale_modifier, background, image, nullptr, 3, nullptr, max_instances, count, w + L.fwd,
+                                 L.fwd_bytes, stream, nullptr);
+    if (st != 0) return st;
+    st = sixdgs_photometric_loss(image, 4, target, target_is_u8, target_stride, views, width, height, lambda, nullptr, loss, nullptr,
+                                 last ? nullptr : grad, w + L.photo, L.photo_bytes, stream, nullptr);
+    if (st != 0) return st;
+    if (!last) {
+      st = sixdgs_raster_views_backward(xyz, scale, scale_is_log, rot, opacity, opacity_is_logit, f_dc, f_rest, sh_degree, n_coef, n, rows,
+                                        views, width, height, scale_modifier, background, grad, max_instances, w + L.fwd, L.fwd_bytes, nullptr,
+                                        nullptr, nullptr, nullptr, nullptr, nullptr, d_rows, w + L.bwd, L.bwd_bytes, stream, nullptr);
+      if (st != 0) return st;
+    }
+    const StepArgs A = {start_rows, loss,  last ? nullptr : d_rows, count, max_instances, views, step, last, ps::adam_at(step, lr, beta1, beta2, eps),
+                        dl,         m,     v,    rows,  best_loss, best_step, best_rows, history + (size_t)step * views, status,
+                        instances_needed};
+    st = launch_step(A, s);
+    if (st != 0) return st;
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -534,6 +534,183 @@ def photometric_loss(image: torch.Tensor, target: torch.Tensor, *, lambda_dssim:
 
 
 # ---------------------------------------------------------------------------------------------
+# pose refinement below the C ABI
+# ---------------------------------------------------------------------------------------------
+POSE_STATE = (("delta", 6, torch.float32), ("m", 6, torch.float32), ("v", 6, torch.float32), ("rows", 16, torch.float32),
+              ("best_loss", 0, torch.float32), ("best_step", 0, torch.int32), ("best_rows", 16, torch.float32), ("status", 0, torch.int32))
+POSE_STATUS_NOT_FINITE, POSE_STATUS_CAPACITY = 1, 2
+REFINE_ATTEMPTS = 4                 # runs of refine_poses_raw before it gives up on the instance capacity
+
+
+def _check_adam(lr, beta1, beta2, eps):
+    if not (0.0 < float(lr) < float("inf")):
+        raise ValueError(f"lr must be positive and finite (got {lr})")
+    if not (0.0 <= float(beta1) < 1.0 and 0.0 <= float(beta2) < 1.0):
+        raise ValueError(f"beta1 and beta2 must be in [0, 1) (got {beta1}, {beta2})")
+    if not (0.0 <= float(eps) < float("inf")):
+        raise ValueError(f"eps must be non-negative and finite (got {eps})")
+
+
+def _check_rows(t, name, width=16):
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != width or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 [views,{width}] tensor")
+
+
+@_on_device
+def pose_compose(start: torch.Tensor, delta: torch.Tensor) -> torch.Tensor:
+    """rows [V,16] = the camera rows start [V,16] with the rigid motions delta [V,6] = (translation, axis-angle) applied after their
+    w2c (sixdgs_pose_compose in include/sixdgs.h defines it operation by operation)."""
+    _check_rows(start, "start")
+    _check_rows(delta, "delta", 6)
+    if delta.shape[0] != start.shape[0]:
+        raise ValueError("start and delta disagree about the number of views")
+    _need_gpu(start, delta)
+    rows = torch.empty_like(start)
+    check(_lib.load().sixdgs_pose_compose(_p(start), _p(delta), start.shape[0], _p(rows), _stream()), "pose_compose")
+    return rows
+
+
+@_on_device
+def pose_state(start: torch.Tensor) -> dict:
+    """The state sixdgs_pose_step starts from, for start [V,16]: delta = m = v = 0, rows = pose_compose(start, 0), best_loss = +inf,
+    best_step = 0, best_rows = start, status = 0, instances_needed = 0 (int64 [1])."""
+    _check_rows(start, "start")
+    _need_gpu(start)
+    views, dev = start.shape[0], start.device
+    z = torch.zeros(views, 6, device=dev)
+    return {"delta": z, "m": z.clone(), "v": z.clone(), "rows": pose_compose(start, z), "best_loss": torch.full((views,), float("inf"), device=dev),
+            "best_step": torch.zeros(views, dtype=torch.int32, device=dev), "best_rows": start.clone(),
+            "status": torch.zeros(views, dtype=torch.int32, device=dev), "instances_needed": torch.zeros(1, dtype=torch.int64, device=dev)}
+
+
+@_on_device
+def pose_step(start: torch.Tensor, loss: torch.Tensor, d_rows: Optional[torch.Tensor], state: dict, history_row: torch.Tensor, step: int, *,
+              instances: Optional[torch.Tensor] = None, max_instances: int = RASTER_MAX_INSTANCES, evaluate_only: bool = False,
+              lr: float = 2e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8) -> None:
+    """Step `step` of a refinement (sixdgs_pose_step in include/sixdgs.h): records loss [V] of the iterate in state["rows"] into
+    history_row [V], keeps the first minimum, and -- unless evaluate_only -- chains d_rows [V,16] to the 6-vector, takes one Adam step
+    and writes the next iterate's rows.  `state` is pose_state's dict, UPDATED IN PLACE; instances: the int64 [1] count a rasteriser
+    call left on the device, checked against max_instances."""
+    _check_rows(start, "start")
+    views = start.shape[0]
+    if isinstance(step, bool) or int(step) != step or int(step) < 0:
+        raise ValueError(f"step must be a non-negative integer (got {step})")
+    _check_adam(lr, beta1, beta2, eps)
+    if not 1 <= int(max_instances) <= RASTER_MAX_INSTANCES:
+        raise ValueError(f"max_instances must be in [1, 2^31) (got {max_instances})")
+    for name, t in (("loss", loss), ("history_row", history_row)):
+        if not torch.is_tensor(t) or tuple(t.shape) != (views,) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 [{views}] tensor")
+    if evaluate_only:
+        d_rows = None
+    else:
+        _check_rows(d_rows, "d_rows")
+        if d_rows.shape[0] != views:
+            raise ValueError("start and d_rows disagree about the number of views")
+    for name, width, dtype in POSE_STATE:
+        t = state.get(name) if isinstance(state, dict) else None
+        if (not torch.is_tensor(t) or tuple(t.shape) != ((views, width) if width else (views,)) or t.dtype != dtype or not t.is_contiguous()):
+            raise ValueError(f"state[{name!r}] must be a contiguous {dtype} tensor of {views} views (ops.pose_state makes the dict)")
+    needed = state.get("instances_needed")
+    if not torch.is_tensor(needed) or tuple(needed.shape) != (1,) or needed.dtype != torch.int64:
+        raise ValueError("state['instances_needed'] must be an int64 [1] tensor")
+    if instances is not None and (not torch.is_tensor(instances) or tuple(instances.shape) != (1,) or instances.dtype != torch.int64):
+        raise ValueError("instances must be an int64 [1] tensor")
+    _need_gpu(start, loss, d_rows, history_row, instances, needed, *[state[name] for name, _, _ in POSE_STATE])
+    check(_lib.load().sixdgs_pose_step(_p(start), _p(loss), _p(d_rows), _p(instances), int(max_instances), views, int(step), int(bool(evaluate_only)),
+                                       float(lr), float(beta1), float(beta2), float(eps), _p(state["delta"]), _p(state["m"]), _p(state["v"]),
+                                       _p(state["rows"]), _p(state["best_loss"]), _p(state["best_step"]), _p(state["best_rows"]), _p(history_row),
+                                       _p(state["status"]), _p(needed), _stream()), "pose_step")
+
+
+def refine_poses_workspace_bytes(n: int, views: int, width: int, height: int, max_instances: int) -> int:
+    return int(_lib.load().sixdgs_refine_poses_workspace_bytes(int(n), int(views), int(width), int(height), int(max_instances)))
+
+
+@_on_device
+def refine_poses_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, start_rows: torch.Tensor, width: int, height: int,
+                     target: torch.Tensor, *, steps: int, lambda_dssim: float = 0.2, lr: float = 2e-3, beta1: float = 0.9, beta2: float = 0.999,
+                     eps: float = 1e-8, scale_modifier: float = 1.0, background=(1.0, 1.0, 1.0), scale_is_log: bool = True,
+                     opacity_is_logit: bool = True, max_instances: Optional[int] = None, retry: bool = True) -> dict:
+    """Render-and-compare refinement of the camera rows start_rows [V,16] as ONE library call (sixdgs_refine_poses in include/sixdgs.h):
+    steps + 1 evaluations and `steps` Adam updates, enqueued without a host read.  target: fp32 [V,height,width,3|4] or uint8
+    [V,height,width,3].  Returns a dict: best_rows [V,16], best_loss [V], best_step [V] (int32), history [steps + 1,V], delta [V,6] (the
+    last iterate's motion), status [V] (int32; bit 0: a loss or gradient was not finite, bit 1: the instance capacity was too small),
+    instances_needed (int) and max_instances (int: the capacity of the run returned).  The call runs with raster_instances_estimate's capacity (or max_instances), reads status and
+    instances_needed once at the end, and -- with retry -- on bit 1 runs again from the start with 5/4 of the needed capacity, at most
+    REFINE_ATTEMPTS runs in all, then RuntimeError."""
+    lam = float(lambda_dssim)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_dssim must be in [0, 1] (got {lambda_dssim})")
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+        raise ValueError(f"steps must be a positive integer (got {steps})")
+    _check_adam(lr, beta1, beta2, eps)
+    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
+        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
+    if int(width) < 1 or int(height) < 1:
+        raise ValueError(f"width and height must be positive (got {width} x {height})")
+    if len(background) != 3:
+        raise ValueError("background must have 3 entries")
+    if max_instances is not None and not 1 <= int(max_instances) <= RASTER_MAX_INSTANCES:
+        raise ValueError(f"max_instances must be in [1, 2^31) (got {max_instances})")
+    if not torch.is_tensor(start_rows) or start_rows.dim() != 2 or start_rows.shape[1] != 16:
+        raise ValueError("start_rows must be a [views,16] tensor")
+    xyz, scale, rot, opacity, f_dc, f_rest, start_rows = (_f32(xyz), _f32(scale), _f32(rot), _f32(opacity), _f32(f_dc), _f32(f_rest),
+                                                          _f32(start_rows))
+    n, views, steps, width, height = xyz.shape[0], start_rows.shape[0], int(steps), int(width), int(height)
+    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
+    if (xyz.shape != (n, 3) or scale.shape != (n, 3) or rot.shape != (n, 4) or opacity.numel() != n or f_dc.numel() != 3 * n
+            or f_rest.numel() != 3 * n * (n_coef - 1)):
+        raise ValueError("scene arrays disagree about the number of Gaussians")
+    if not torch.is_tensor(target) or target.dim() != 4 or tuple(target.shape[:3]) != (views, height, width):
+        raise ValueError(f"target must be a [{views},{height},{width},3|4] tensor")
+    if target.dtype == torch.uint8:
+        if target.shape[3] != 3:
+            raise ValueError("a uint8 target must have 3 channels")
+    elif target.dtype != torch.float32 or target.shape[3] not in (3, 4):
+        raise ValueError("target must be float32 with 3 or 4 channels, or uint8 with 3")
+    if not target.is_contiguous():
+        raise ValueError("target must be contiguous")
+    target = target.detach()
+    _need_gpu(xyz, scale, rot, opacity, f_dc, f_rest, start_rows, target)
+    lib = _lib.load()
+    dev = xyz.device
+    bg = torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
+    out = {"best_rows": torch.empty(views, 16, device=dev), "best_loss": torch.empty(views, device=dev),
+           "best_step": torch.empty(views, dtype=torch.int32, device=dev), "history": torch.empty(steps + 1, views, device=dev),
+           "delta": torch.empty(views, 6, device=dev), "status": torch.empty(views, dtype=torch.int32, device=dev)}
+    needed_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    capacity = int(max_instances) if max_instances is not None else raster_instances_estimate(n, views)
+    needed = 0
+    for attempt in range(REFINE_ATTEMPTS):
+        need = lib.sixdgs_refine_poses_workspace_bytes(n, views, width, height, capacity)
+        if need == 0:
+            raise ValueError(f"sizes outside the rasteriser's limits (n {n}, views {views}, {width} x {height}, instances {capacity})")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib.sixdgs_refine_poses(_p(xyz), _p(scale), int(scale_is_log), _p(rot), _p(opacity), int(opacity_is_logit), _p(f_dc),
+                                      _p(f_rest if n_coef > 1 else None), int(sh_degree), int(n_coef), n, _p(start_rows), views, width, height,
+                                      float(scale_modifier), _p(bg), _p(target), int(target.dtype == torch.uint8), int(target.shape[3]), lam,
+                                      steps, float(lr), float(beta1), float(beta2), float(eps), capacity, _p(out["best_rows"]),
+                                      _p(out["best_loss"]), _p(out["best_step"]), _p(out["history"]), _p(out["delta"]), _p(out["status"]),
+                                      _p(needed_t), _p(ws), need, _stream()),
+              "refine_poses")
+        if views == 0:
+            break
+        # the one host read of the call: every status word and the largest instance count seen
+        flags = torch.cat([out["status"].to(torch.int64), needed_t]).cpu()
+        needed = int(flags[-1])
+        if not retry or not bool((flags[:-1] & POSE_STATUS_CAPACITY).any()):
+            break
+        if attempt == REFINE_ATTEMPTS - 1 or needed > RASTER_MAX_INSTANCES:
+            raise RuntimeError(f"6dgs_amd: refine_poses still needs {needed} tile instances after {attempt + 1} runs (limit 2^31 - 1): "
+                               "refine fewer views at once")
+        capacity = min(max(needed + needed // 4, 1), RASTER_MAX_INSTANCES)
+    out["instances_needed"] = needed
+    out["max_instances"] = capacity
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # scorer
 # ---------------------------------------------------------------------------------------------
 class PackedWeights:

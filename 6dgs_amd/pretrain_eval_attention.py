@@ -17,7 +17,7 @@ Beyond the reference (keyword-only / extra flags, defaults reproduce it): --emit
 full-scene emission (every Gaussian) instead of the reference's 1000-ellipsoid subsample; --skip_train evaluates random-init
 weights when no checkpoint exists (smoke runs); --n_iterations shortens training; --pose_solver consensus (with --inlier_scale and
 --rays_to_output, up to 1024) solves the pose with the consensus solver (ops.solve_pose_consensus) instead of least squares;
---refine_steps N (with --refine_downscale, --refine_lr, --refine_lambda) refines every estimated pose by render-and-compare
+--refine_steps N (with --refine_downscale, --refine_lr, --refine_lambda, --refine_backend) refines every estimated pose by render-and-compare
 (refine.refine_results) on each rank's block and adds the refined_* and photometric_loss_* keys to its result dicts; the mean and
 median errors before and after go to <out_path>.refine_summary.json.  0, the default: no refinement, results.json as without the flag.
 """
@@ -81,6 +81,9 @@ def parse_args(argv=None):
     ap.add_argument("--refine_downscale", type=int, default=4, help="refinement compares at 1 / this of the query's resolution")
     ap.add_argument("--refine_lr", type=float, default=2e-3, help="Adam step of the refinement")
     ap.add_argument("--refine_lambda", type=float, default=0.2, help="weight of D-SSIM in the refinement's loss (the reference's lambda_dssim)")
+    # (absent from the namespace unless given: a command line without it parses to exactly what it did before the flag existed)
+    ap.add_argument("--refine_backend", choices=("torch", "fused"), default=argparse.SUPPRESS,
+                    help="the refinement's loop: torch (default; autograd and Adam around the kernels) or fused (one library call, sixdgs_refine_poses)")
     args, rest = ap.parse_known_args(argv)
     if args.refine_steps < 0:
         ap.error("--refine_steps must be >= 0 (0 = no refinement)")
@@ -135,7 +138,7 @@ def pretrain_single_object(checkpoint_filepath: str, checkpoint_args: "dotdict[s
     the same stage; the ranks of a failing iteration leave it together.
 
     pose_solver / inlier_scale / rays_to_output: handed to both passes of test_pose_estimation.  refine: the keyword arguments of
-    refine.refine_poses (steps, lr, lambda_dssim, downscale); when given, each rank refines the poses of its block after the inference
+    refine.refine_poses (steps, lr, lambda_dssim, downscale, backend); when given, each rank refines the poses of its block after the inference
     pass (refine.refine_results).  None: no refinement."""
     solver = dict(pose_solver=pose_solver, inlier_scale=inlier_scale, rays_to_output=rays_to_output)
     torch.manual_seed(starting_seed)
@@ -276,7 +279,8 @@ def main(argv=None, backbone: Optional[torch.nn.Module] = None) -> List[dict]:
                 batched_window=args.batched_window, data_parallel_train=args.data_parallel_train,
                 backward_ray_groups=args.backward_ray_groups, pose_solver=args.pose_solver, inlier_scale=args.inlier_scale,
                 rays_to_output=args.rays_to_output,
-                refine=dict(steps=args.refine_steps, lr=args.refine_lr, lambda_dssim=args.refine_lambda, downscale=args.refine_downscale)
+                refine=dict(steps=args.refine_steps, lr=args.refine_lr, lambda_dssim=args.refine_lambda, downscale=args.refine_downscale,
+                            backend=getattr(args, "refine_backend", "torch"))
                 if args.refine_steps > 0 else None)
             if rank == 0:
                 results.extend(obj)

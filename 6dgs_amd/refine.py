@@ -4,6 +4,10 @@ pose, looks like the query image.
     refine_poses(scene, images, c2w, intrinsics)      Adam on a 6-vector per view under (1 - lambda) L1 + lambda (1 - SSIM)
     refine_results(scene, cameras_info, results)      the same as a post-pass over the list test_pose_estimation returns
 
+Two backends run the same loop.  "torch" (the default) is described next; "fused" hands the whole loop to the library
+(ops.refine_poses_raw -> sixdgs_refine_poses: the same three kernels per step, the pose arithmetic as HIP kernels, nothing read back
+until the end), so its iterates differ from the torch ones by rounding only.
+
 Per step: autograd.raster_views draws every view (sixdgs_raster_views), autograd.photometric_loss compares it with the target
 (sixdgs_photometric_loss, one call for loss and gradient), the rasteriser's backward gives the camera rows' gradient
 (sixdgs_raster_views_backward), and torch chains it through `compose` to the 6-vector.  Views never mix: the image, the loss, the
@@ -21,7 +25,10 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
-from . import autograd
+from . import autograd, ops
+
+BACKENDS = ("torch", "fused")
+ALPHA_MODES = ("ignore", "composite")
 
 
 def rodrigues(w: torch.Tensor) -> torch.Tensor:
@@ -52,19 +59,33 @@ def compose(row: torch.Tensor, delta: torch.Tensor) -> torch.Tensor:
     return torch.cat([moved.reshape(*row.shape[:-1], 12), row[..., 12:]], dim=-1)
 
 
-def prepare_target(images_u8: torch.Tensor, downscale: int):
+def prepare_target(images_u8: torch.Tensor, downscale: int, alpha: str = "ignore", background=(1.0, 1.0, 1.0)):
     """images_u8 uint8 [V,H,W,3|4] -> (target, crop_x, crop_y): with downscale 1 the rgb bytes themselves (uint8 [V,H,W,3], which the
     loss reads as u / 255); otherwise fp32 [V,H // d,W // d,3], the mean of u / 255 over d x d blocks of the centred crop that starts at
-    (crop_x, crop_y) = ((W mod d) // 2, (H mod d) // 2)."""
+    (crop_x, crop_y) = ((W mod d) // 2, (H mod d) // 2).  alpha says what the fourth channel of an RGBA image means: "ignore" takes the
+    rgb bytes as they lie; "composite" sets the value to rgb a + (1 - a) background with a = u / 255 before the blocks are averaged --
+    what test.prepare_image feeds the backbone, and what a render over that background looks like (the target is then fp32 at
+    downscale 1 too).  Images without a fourth channel are the same under both."""
+    if alpha not in ALPHA_MODES:
+        raise ValueError(f"alpha must be one of {ALPHA_MODES} (got {alpha!r})")
+    if len(background) != 3:
+        raise ValueError("background must have 3 entries")
     d = int(downscale)
     v, h, w, _ = images_u8.shape
-    if d == 1:
+    composite = alpha == "composite" and images_u8.shape[3] == 4
+    if d == 1 and not composite:
         return images_u8[..., :3].contiguous(), 0, 0
     hh, ww = h // d, w // d
     if hh < 1 or ww < 1:
         raise ValueError(f"downscale {d} leaves nothing of a {w} x {h} image")
     oy, ox = (h - hh * d) // 2, (w - ww * d) // 2
-    x = images_u8[:, oy:oy + hh * d, ox:ox + ww * d, :3].float() / 255.0
+    crop = images_u8[:, oy:oy + hh * d, ox:ox + ww * d]
+    x = crop[..., :3].float() / 255.0
+    if composite:
+        a = crop[..., 3:].float() / 255.0
+        x = x * a + (1.0 - a) * torch.tensor([float(b) for b in background], dtype=torch.float32, device=x.device)
+    if d == 1:
+        return x.contiguous(), ox, oy
     return x.reshape(v, hh, d, ww, d, 3).mean(dim=(2, 4)).contiguous(), ox, oy
 
 
@@ -110,13 +131,27 @@ def _stack_images(images, dev) -> torch.Tensor:
     return torch.stack([t.to(dev) for t in out])
 
 
+def _rows_to_c2w(best_rows: torch.Tensor, best_step: torch.Tensor, c2w: torch.Tensor) -> torch.Tensor:
+    """The c2w [V,4,4] of the best camera rows (inverted on the host); the input pose itself where the best step is 0."""
+    views, dev = c2w.shape[0], c2w.device
+    w2c = torch.eye(4).repeat(views, 1, 1)
+    w2c[:, :3, :] = best_rows[:, :12].reshape(views, 3, 4).cpu()
+    return torch.where((best_step == 0)[:, None, None], c2w, torch.linalg.inv(w2c).to(dev))
+
+
 def refine_poses(scene, images, c2w, intrinsics, *, steps: int = 100, lr: float = 2e-3, lambda_dssim: float = 0.2, downscale: int = 4,
-                 background=(1.0, 1.0, 1.0), scale_modifier: float = 1.0) -> dict:
+                 background=(1.0, 1.0, 1.0), scale_modifier: float = 1.0, backend: str = "torch", alpha: str = "ignore") -> dict:
     """Refine the poses c2w [V,4,4] of the query `images` (uint8 [H,W,3|4] arrays or GPU tensors of one size) against `scene`
     (a GaussianScene on the GPU).  intrinsics: K [3,3] or [V,3,3] as test.gt_pose_and_intrinsics gives it.  Adam (lr) for `steps`
     steps on [V,6], objective photometric_loss(raster_views(...)).sum() at 1 / downscale of the resolution.
     Returns a dict of tensors on the scene's device: c2w [V,4,4] -- per view the iterate with the lowest loss, the input pose itself
-    where no step lowered it --, loss_start [V], loss_best [V], best_step [V] (int64) and loss_history [steps + 1, V]."""
+    where no step lowered it --, loss_start [V], loss_best [V], best_step [V] (int64) and loss_history [steps + 1, V].
+    backend "fused" runs the loop as one library call (ops.refine_poses_raw) and adds status [V] (int32, 0 = fine; bit 0: the view met a
+    loss or gradient that was not finite and stopped moving there).  alpha: prepare_target's, with this call's background."""
+    if backend not in BACKENDS:
+        raise ValueError(f"backend must be one of {BACKENDS} (got {backend!r})")
+    if alpha not in ALPHA_MODES:
+        raise ValueError(f"alpha must be one of {ALPHA_MODES} (got {alpha!r})")
     if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
         raise ValueError(f"steps must be a positive integer (got {steps})")
     if not (float(lr) > 0.0 and float(lr) < float("inf")):
@@ -147,11 +182,17 @@ def refine_poses(scene, images, c2w, intrinsics, *, steps: int = 100, lr: float 
         raise RuntimeError("6dgs_amd: refine_poses needs the scene on the GPU (no CPU fallback on the product path)")
     dev = tensors[0].device
     tensors = tuple(t.detach() for t in tensors)
-    target, ox, oy = prepare_target(_stack_images(images, dev), downscale)
+    target, ox, oy = prepare_target(_stack_images(images, dev), downscale, alpha, background)
     height, width = int(target.shape[1]), int(target.shape[2])
     # (the two 4 x 4 inversions run on the host, as test.gt_pose_and_intrinsics' does)
     start = torch.cat([torch.linalg.inv(c2w.cpu())[:, :3, :].reshape(views, 12), scaled_intrinsics(K.cpu(), downscale, ox, oy)], dim=1).to(dev).contiguous()
     c2w = c2w.to(dev)
+    if backend == "fused":
+        raw = ops.refine_poses_raw(*tensors, sh_degree, start, width, height, target, steps=steps, lambda_dssim=float(lambda_dssim), lr=float(lr),
+                                   background=background, scale_modifier=scale_modifier)
+        out = _rows_to_c2w(raw["best_rows"], raw["best_step"], c2w)
+        return {"c2w": out, "loss_start": raw["history"][0].clone(), "loss_best": raw["best_loss"], "best_step": raw["best_step"].to(torch.int64),
+                "loss_history": raw["history"], "status": raw["status"]}
     delta = torch.zeros(views, 6, device=dev, requires_grad=True)
     opt = torch.optim.Adam([delta], lr=float(lr))
     history = torch.empty(steps + 1, views, device=dev)
@@ -175,9 +216,7 @@ def refine_poses(scene, images, c2w, intrinsics, *, steps: int = 100, lr: float 
             opt.zero_grad()
             loss.sum().backward()
             opt.step()
-    w2c = torch.eye(4).repeat(views, 1, 1)
-    w2c[:, :3, :] = best_rows[:, :12].reshape(views, 3, 4).cpu()
-    out = torch.where((best_step == 0)[:, None, None], c2w, torch.linalg.inv(w2c).to(dev))
+    out = _rows_to_c2w(best_rows, best_step, c2w)
     return {"c2w": out, "loss_start": history[0].clone(), "loss_best": best, "best_step": best_step, "loss_history": history}
 
 
@@ -186,7 +225,7 @@ def refine_results(scene, cameras_info: Sequence, results: List[dict], *, batch_
     entry with a finite pred_c2w gains refined_c2w, refined_translation_error, refined_angular_error (against its gt_c2w),
     photometric_loss_before and photometric_loss_after; existing keys are untouched.  ValueError when a camera's image is not of the
     camera's width x height (its intrinsics would not be the image's).  Views of one image size are refined
-    `batch_size` at a time; kw goes to refine_poses."""
+    `batch_size` at a time; kw goes to refine_poses (backend and alpha among it)."""
     from .test import gt_pose_and_intrinsics
 
     if len(results) != len(cameras_info):

@@ -331,6 +331,90 @@ int sixdgs_photometric_loss(const float* image /*[views][height][width][image_st
                             sixdgs_profile* prof);
 
 /* ---------------------------------------------------------------------------------------------
+ * The pose arithmetic of render-and-compare refinement (additive in ABI 10): a rigid motion delta[v] = (dt, w) -- translation, then
+ * axis-angle -- applied AFTER a view's starting w2c, its exact derivative, Adam on the six numbers, and the bookkeeping of the best
+ * iterate.  All arithmetic in fp32, no contraction into fused multiply-adds; one thread per view, one owner per output, no atomics;
+ * views never mix: row v of every output is the same bits whether view v is passed alone or in a batch.
+ *
+ * COMPOSE.  start[v] = 16 floats: w2c rows 0..2 = [R | t] (12 floats, row-major 3 x 4), then fx, fy, cx, cy.
+ *   1. x = (w0 w0 + w1 w1) + w2 w2 (= theta^2); K = [w]x = [[0, -w2, w1], [w2, 0, -w0], [-w1, w0, 0]];
+ *   2. a = sin th / th, b = (1 - cos th) / th^2, c = (th - sin th) / th^3.  For x < 1: Horner in x over k = 5 .. 0 with the fp32
+ *      coefficients (-1)^k / (2k + 1)!, (-1)^k / (2k + 2)!, (-1)^k / (2k + 3)! (each the fp32 quotient of 1 and the factorial):
+ *      a = 1 + x (-1/6 + x (1/120 + x (-1/5040 + x (1/362880 + x (-1/39916800))))) and likewise b from 1/2, c from 1/6; the first
+ *      dropped term is below 2e-10 of the value.  For x >= 1: th = sqrt(x), s = sin th, h = sin(th / 2), a = s / th,
+ *      b = (2 (h h)) / x, c = (th - s) / (x th) -- no cancellation in b, and th - s keeps at least th / 6;
+ *   3. every 3 x 3 product is three terms added in index order, (p_i0 q_0j + p_i1 q_1j) + p_i2 q_2j; K2 = K K;
+ *      dR_ij = ((i == j ? 1 : 0) + a K_ij) + b K2_ij;
+ *   4. rows[v] = [dR R | dR t + dt | fx fy cx cy]: the 3 x 4 product dR [R | t] as in 3, then dt added to its fourth column.
+ *   delta = 0 returns start bit for bit (for finite start; a -0 entry comes back as +0).
+ *
+ * CHAIN RULE.  G = the 3 x 4 part of d_rows[v] = dL / d rows[v] (its intrinsics entries are ignored), [R | t] of start[v]:
+ *   d dt = G[:, 3];  A_ir = ((G_i0 R_r0 + G_i1 R_r1) + G_i2 R_r2) + G_i3 t_r;  M = A dR^T (as in 3);
+ *   tau = (M_21 - M_12, M_02 - M_20, M_10 - M_01);  k1 = w x tau, k2 = w x k1 (cross products: u1 v2 - u2 v1, ...);
+ *   d w_i = (tau_i - b k1_i) + c k2_i.  This is the exact derivative of COMPOSE.
+ *
+ * ADAM (torch.optim.Adam's plain form), step t = step + 1, per entry g of the six:
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) (g g);  delta = delta - (lr / c1) (m / (sqrt(v) / c2 + eps)),
+ *   c1 = 1 - beta1^t and c2 = sqrt(1 - beta2^t) formed by the host in double from the float arguments and rounded to float.
+ *
+ * sixdgs_pose_compose writes rows [views][16] from start [views][16] and delta [views][6] (rows must not be start).
+ *
+ * sixdgs_pose_step is step `step` (>= 0) of a refinement: `rows` holds iterate `step`, loss [views] its loss, d_rows [views][16]
+ * dL / d rows (not read, may be NULL, with evaluate_only = 1).  With count = *instances (0 when instances is NULL), per view v:
+ *   1. view 0 alone: instances_needed[0] = max(instances_needed[0], count);
+ *   2. if count > max_instances, bit 1 of status[v] is set.  While bit 1 is set NOTHING of a step is recorded: history_row[v] = NaN
+ *      and the view returns -- the images of an overflowed step are unspecified, so every view is frozen from then on;
+ *   3. history_row[v] = loss[v]; if loss[v] < best_loss[v] (strict: the first minimum is kept; never true for NaN):
+ *      best_loss[v] = loss[v], best_step[v] = step, best_rows[v] = rows[v];
+ *   4. if loss[v] or -- without evaluate_only -- any of the 12 w2c entries of d_rows[v] is not finite, bit 0 of status[v] is set.
+ *      A view with bit 0 set is frozen: delta, m, v and rows no longer change (steps 1 - 3 go on);
+ *   5. otherwise, without evaluate_only: CHAIN RULE, ADAM, and rows[v] = COMPOSE(start[v], delta[v]), the next iterate.
+ * The caller owns the state and starts it as delta = m = v = 0, rows = COMPOSE(start, 0), best_loss = +inf, best_step = 0,
+ * best_rows = start, status = 0, instances_needed = 0.  history_row is the caller's history + step * views.
+ * Limits: views <= 65535, 1 <= max_instances < 2^31, lr > 0 finite, beta1, beta2 in [0, 1), eps >= 0 finite.  SIXDGS_E_BADARG without a
+ * launch for argument errors (a NULL array, rows == start, rows == best_rows included); views == 0 returns 0. */
+int sixdgs_pose_compose(const float* start /*[views][16]*/, const float* delta /*[views][6]*/, int views, float* rows /*[views][16]*/,
+                        sixdgs_stream_t stream);
+int sixdgs_pose_step(const float* start /*[views][16]*/, const float* loss /*[views]*/, const float* d_rows /*[views][16] or NULL*/,
+                     const int64_t* instances /*[1] device or NULL*/, int64_t max_instances, int views, int step, int evaluate_only,
+                     float lr, float beta1, float beta2, float eps, float* delta /*[views][6]*/, float* m /*[views][6]*/,
+                     float* v /*[views][6]*/, float* rows /*[views][16] in: iterate step, out: iterate step + 1*/,
+                     float* best_loss /*[views]*/, int32_t* best_step /*[views]*/, float* best_rows /*[views][16]*/,
+                     float* history_row /*[views]*/, int32_t* status /*[views]*/, int64_t* instances_needed /*[1]*/,
+                     sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Render-and-compare pose refinement as one call (additive in ABI 10).  Starts the state as sixdgs_pose_step describes, then for
+ * s = 0 .. steps enqueues on `stream`, in this order and through the entry points above as they are:
+ *   1. sixdgs_raster_views of the current rows (float image only; the instance count is left on the device);
+ *   2. sixdgs_photometric_loss against the target (lambda; with grad_image, grad_loss = 1, except at s = steps);
+ *   3. sixdgs_raster_views_backward with only d_cams wanted (skipped at s = steps);
+ *   4. sixdgs_pose_step (evaluate_only at s = steps) with that count, max_instances and history + s * views.
+ * So iterate s is evaluated at step s, steps Adam updates are made, and history has steps + 1 rows.  The call makes no host
+ * synchronisation, no device-to-host copy and no allocation; the library stays stateless; when it returns, the work is enqueued.
+ * Scene arrays, flags, scale_modifier and background (device [3]) as sixdgs_raster_views takes them; start_rows [views][16] as cams;
+ * the target in the three forms sixdgs_photometric_loss takes, of size width x height.
+ * Outputs (device, all required except delta): best_rows [views][16], best_loss [views], best_step [views] int32, history
+ * [steps + 1][views], delta [views][6] = the last iterate's motion (may be NULL), status [views] (bit 0: not finite, bit 1: capacity),
+ * instances_needed [1] = the largest instance count seen.  When max_instances was too small at some step, bit 1 is set in every
+ * status[v], that step and all later ones record nothing (their history rows are NaN; best_* are those of the steps before,
+ * best_step = 0 and best_rows = start_rows when it was step 0): call again with max_instances >= instances_needed[0].
+ * SAME INPUT, SAME BYTES; row v of every output is the same bits whether view v is refined alone or in a batch, given a capacity that
+ * fits.  Limits are the parts': the rasteriser's sizes, lambda in [0, 1], 1 <= steps, the Adam limits of sixdgs_pose_step.
+ * SIXDGS_E_BADARG for argument errors, SIXDGS_E_WORKSPACE for too small a workspace, both without touching a GPU; views == 0 returns 0.
+ * sixdgs_refine_poses_workspace_bytes is answered without a GPU and is 0 outside the limits: the three parts' workspaces (the loss's
+ * with the gradient), two float images of views x height x width x 4, and 204 B of state per view (rows, d_rows, loss, delta, m, v) plus the count, each
+ * piece rounded up to 256 B. */
+size_t sixdgs_refine_poses_workspace_bytes(int64_t n, int views, int width, int height, int64_t max_instances);
+int sixdgs_refine_poses(const float* xyz, const float* scale, int scale_is_log, const float* rot, const float* opacity,
+                        int opacity_is_logit, const float* f_dc, const float* f_rest, int sh_degree, int n_coef, int64_t n,
+                        const float* start_rows /*[views][16]*/, int views, int width, int height, float scale_modifier,
+                        const float* background /*[3] device*/, const void* target, int target_is_u8, int target_stride, float lambda,
+                        int steps, float lr, float beta1, float beta2, float eps, int64_t max_instances, float* best_rows, float* best_loss,
+                        int32_t* best_step, float* history, float* delta /*or NULL*/, int32_t* status, int64_t* instances_needed, void* ws,
+                        size_t ws_bytes, sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scorer, scene side (once per scene): ray MLP + k_proj -> key cache
  * replaces RayPreprocessor.forward (ray_preprocessor.py:36-46) + k_proj (our_multihead_attention.py:74)
  * ------------------------------------------------------------------------------------------- */

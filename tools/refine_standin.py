@@ -1,6 +1,6 @@
 """Measure pose refinement (6dgs_amd/refine.py) on a stand-in scene.
 
-    python tools/refine_standin.py [--gaussians 5000] [--size 224] [--views 8] [--steps 100] [--downscale 2] [--iterations 600]
+    python tools/refine_standin.py [--gaussians 5000] [--size 224] [--views 8] [--steps 100] [--downscale 2] [--iterations 600] [--backend torch|fused]
 
 Builds synthetic.make_scene, renders held-out views with renderer="raster" (so the query images are the scene's own renderer's), and
 refines from two kinds of start:
@@ -10,8 +10,9 @@ refines from two kinds of start:
               functions, `iterations` iterations; 0 skips this part)
 Reports per kind the centre and rotation error before and after (median and how many views improved), the loss before and after, and
 the milliseconds of a refinement step split into raster forward, loss, raster backward and the rest (HIP events around each part
-of a hand-written step on the same views; the rest is compose, its autograd, Adam and the host in between).  Nothing is asserted:
-what comes out is reported, a negative result included."""
+of a hand-written step on the same views; the rest is compose, its autograd, Adam and the host in between).
+--backend fused runs every refinement as one library call (refine_poses(..., backend="fused")); the split is of the torch step either way.
+Nothing is asserted: what comes out is reported, a negative result included."""
 import argparse
 import importlib
 import os
@@ -82,6 +83,7 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--downscale", type=int, default=2)
     ap.add_argument("--iterations", type=int, default=600, help="training iterations of the stand-in scorer (0: skip the estimator part)")
+    ap.add_argument("--backend", choices=("torch", "fused"), default="torch", help="refine.refine_poses' backend")
     ap.add_argument("--ckpt", default=os.path.join(tempfile.gettempdir(), "refine_standin_id_module.th"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -94,8 +96,9 @@ def main():
     gt, K = torch.stack(gt), torch.stack(Ks)
     images = [c.image for c in held]
     rows = torch.from_numpy(importlib.import_module("6dgs_amd.render").camera_rows(held))
-    kw = dict(steps=args.steps, downscale=args.downscale)
-    print(f"{args.gaussians} Gaussians, {args.views} held-out {args.size} x {args.size} views (renderer raster), {args.steps} steps, downscale {args.downscale}")
+    kw = dict(steps=args.steps, downscale=args.downscale, backend=args.backend)
+    print(f"{args.gaussians} Gaussians, {args.views} held-out {args.size} x {args.size} views (renderer raster), {args.steps} steps, downscale {args.downscale}, "
+          f"backend {args.backend}")
     for name, mult in (("perturbed x 1", 1.0), ("perturbed x 4", 4.0)):
         off = torch.tensor([[mult * o * (1 if v % 2 == 0 else -1) for o in OFFSET] for v in range(args.views)], dtype=torch.float32)
         w2c = torch.eye(4).repeat(args.views, 1, 1)
