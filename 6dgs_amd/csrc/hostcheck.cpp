@@ -1,6 +1,6 @@
 // hostcheck.cpp -- HOST instantiation of device_math.h (the per-thread math of the HIP kernels), of dense_layout.h (the index
-// arithmetic of the ray-MLP chain's operand planes) and of pose_step.h (the per-view arithmetic of pose refinement) behind
-// a tiny C ABI, so the CPU test-suite can compare the product's arithmetic with the oracle and the
+// arithmetic of the ray-MLP chain's operand planes), of pose_step.h (the per-view arithmetic of pose refinement) and of adam_step.h
+// (the per-entry arithmetic of fitting a scene's Gaussians) behind a tiny C ABI, so the CPU test-suite can compare the product's arithmetic with the oracle and the
 // golden vectors without a GPU.  Contains no kernels; never used by the product path.
 #include <stdlib.h>
 
@@ -9,6 +9,7 @@
 #include "dense_layout.h"
 #include "sweep_layout.h"
 #include "pose_step.h"
+#include "adam_step.h"
 using namespace sdg;
 
 extern "C" {
@@ -202,6 +203,27 @@ void hc_ps_step(const float* start, const float* loss, const float* d_rows, cons
   for (int i = 0; i < views; ++i)
     ps::step_view(start + 16 * i, d_rows ? d_rows + 16 * i : nullptr, loss[i], count, max_instances, step, evaluate_only != 0, p, delta + 6 * i,
                   m + 6 * i, v + 6 * i, rows + 16 * i, best_loss + i, best_step + i, best_rows + 16 * i, history_row + i, status + i);
+}
+// ---- adam_step.h: the per-entry arithmetic of fit.hip (tests/test_gaussian_adam_host.py) ----
+// sixdgs_gaussian_adam on the host: the same per-entry function over the six groups (p[k], g[k] NULL: frozen) -> the status bits
+int hc_ga_adam(long long n, int n_coef, int step, float* const* p, const float* const* g, float* m, float* v, const float* lr, float beta1,
+               float beta2, float eps) {
+  const ps::Adam adam = ps::adam_at(step, 0.f, beta1, beta2, eps);
+  int status = 0;
+  long long off = 0;
+  for (int k = 0; k < ga::kGroups; ++k) {
+    const long long count = n * ga::group_width(k, n_coef);
+    if (g[k]) {
+      const ga::Rate r = ga::rate(adam, lr[k]);
+      for (long long i = 0; i < count; ++i)
+        if (!ga::adam_entry(r, g[k][i], p[k][i], m[off + i], v[off + i])) status |= ga::kStatusNotFinite;
+    }
+    off += count;
+  }
+  return status;
+}
+void hc_ga_reset(float* opacity, long long n, int is_logit, float ceiling) {
+  for (long long i = 0; i < n; ++i) opacity[i] = ga::reset_entry(opacity[i], is_logit != 0, ceiling);
 }
 int hc_dl_const(int which) {
   const int v[] = {dl::kSlabB, dl::kPRow, dl::kGran, dl::kGranSlab, dl::kChunkRun};

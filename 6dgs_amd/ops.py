@@ -711,6 +711,239 @@ def refine_poses_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, sta
 
 
 # ---------------------------------------------------------------------------------------------
+# fitting a scene's Gaussians below the C ABI
+# ---------------------------------------------------------------------------------------------
+FIT_GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scale", "rot")      # the order of sixdgs_gaussian_adam, of m / v and of group_mask
+FIT_STATUS_NOT_FINITE, FIT_STATUS_CAPACITY = 1, 2
+
+
+def _check_fit_hyper(beta1, beta2, eps):
+    if not (0.0 <= float(beta1) < 1.0 and 0.0 <= float(beta2) < 1.0):
+        raise ValueError(f"beta1 and beta2 must be in [0, 1) (got {beta1}, {beta2})")
+    if not (0.0 <= float(eps) < float("inf")):
+        raise ValueError(f"eps must be non-negative and finite (got {eps})")
+
+
+def _check_rates(lrs):
+    lrs = [float(x) for x in lrs]
+    if len(lrs) != len(FIT_GROUPS) or not all(0.0 <= x < float("inf") for x in lrs):
+        raise ValueError(f"lrs must be {len(FIT_GROUPS)} non-negative finite rates in the order {FIT_GROUPS} (got {lrs})")
+    return lrs
+
+
+def _fit_params(params, what="params"):
+    """The six arrays of `params` (a dict by FIT_GROUPS' names) -> (n, n_coef); contiguous float32, agreeing about n."""
+    if not isinstance(params, dict) or any(k not in params for k in FIT_GROUPS):
+        raise ValueError(f"{what} must be a dict with the keys {FIT_GROUPS}")
+    for k in FIT_GROUPS:
+        t = params[k]
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{what}[{k!r}] must be a contiguous float32 tensor")
+    n = params["xyz"].shape[0]
+    f_rest = params["f_rest"]
+    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
+    if (params["xyz"].shape != (n, 3) or params["scale"].shape != (n, 3) or params["rot"].shape != (n, 4) or params["opacity"].numel() != n
+            or params["f_dc"].numel() != 3 * n or f_rest.numel() != 3 * n * (n_coef - 1) or not 1 <= n_coef <= 16):
+        raise ValueError("scene arrays disagree about the number of Gaussians")
+    return n, n_coef
+
+
+def gaussian_adam_state(params: dict) -> dict:
+    """The state sixdgs_gaussian_adam starts from, for the six arrays of `params`: m = v = 0 (one buffer each, n (11 + 3 n_coef) floats,
+    group after group in FIT_GROUPS' order) and status = 0 (int32 [1])."""
+    n, n_coef = _fit_params(params)
+    dev = params["xyz"].device
+    size = n * (11 + 3 * n_coef)
+    return {"m": torch.zeros(size, device=dev), "v": torch.zeros(size, device=dev), "status": torch.zeros(1, dtype=torch.int32, device=dev)}
+
+
+def gaussian_adam_slices(n: int, n_coef: int) -> dict:
+    """name -> slice of m / v, in floats."""
+    out, off = {}, 0
+    for k, w in zip(FIT_GROUPS, (3, 3, 3 * (n_coef - 1), 1, 3, 4)):
+        out[k] = slice(off, off + n * w)
+        off += n * w
+    return out
+
+
+def gaussian_adam(params: dict, grads: dict, state: dict, step: int, lrs, *, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-15,
+                  instances: Optional[torch.Tensor] = None, max_instances: int = RASTER_MAX_INSTANCES) -> None:
+    """One Adam step (t = step + 1) over the six parameter arrays of `params`, IN PLACE, as one kernel launch (sixdgs_gaussian_adam in
+    include/sixdgs.h).  params, grads: dicts by FIT_GROUPS' names; grads[k] None (or absent) freezes group k -- its parameters and its
+    slices of m and v stay bit for bit.  lrs: six rates in FIT_GROUPS' order (0 is legal and still updates m and v).  state:
+    gaussian_adam_state's dict, updated in place; status bit 0: a gradient entry was not finite and was left out; bit 1: the count in
+    `instances` (int64 [1], what a rasteriser call left on the device) exceeded max_instances -- that call and every later one changes
+    nothing."""
+    _fit_params(params)
+    return _gaussian_adam(params["xyz"], params, grads, state, step, lrs, beta1, beta2, eps, instances, max_instances)
+
+
+@_on_device
+def _gaussian_adam(anchor, params, grads, state, step, lrs, beta1, beta2, eps, instances, max_instances):
+    """gaussian_adam with the device of `anchor` current (the dicts do not tell _on_device where the call runs)."""
+    n, n_coef = _fit_params(params)
+    if isinstance(step, bool) or int(step) != step or int(step) < 0:
+        raise ValueError(f"step must be a non-negative integer (got {step})")
+    lrs = _check_rates(lrs)
+    _check_fit_hyper(beta1, beta2, eps)
+    if not 1 <= int(max_instances) <= RASTER_MAX_INSTANCES:
+        raise ValueError(f"max_instances must be in [1, 2^31) (got {max_instances})")
+    if not isinstance(grads, dict) or any(k not in FIT_GROUPS for k in grads):
+        raise ValueError(f"grads must be a dict with keys among {FIT_GROUPS}")
+    g = []
+    for k in FIT_GROUPS:
+        t = grads.get(k)
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != params[k].numel()):
+            raise ValueError(f"grads[{k!r}] must be a contiguous float32 tensor of params[{k!r}]'s size")
+        g.append(t)
+    size = n * (11 + 3 * n_coef)
+    for name in ("m", "v"):
+        t = state.get(name) if isinstance(state, dict) else None
+        if not torch.is_tensor(t) or tuple(t.shape) != (size,) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"state[{name!r}] must be a contiguous float32 [{size}] tensor (ops.gaussian_adam_state makes the dict)")
+    status = state.get("status")
+    if not torch.is_tensor(status) or tuple(status.shape) != (1,) or status.dtype != torch.int32:
+        raise ValueError("state['status'] must be an int32 [1] tensor")
+    if instances is not None and (not torch.is_tensor(instances) or tuple(instances.shape) != (1,) or instances.dtype != torch.int64):
+        raise ValueError("instances must be an int64 [1] tensor")
+    _need_gpu(*[params[k] for k in FIT_GROUPS], *g, state["m"], state["v"], status, instances)
+    rates = (C.c_float * len(FIT_GROUPS))(*lrs)
+    check(_lib.load().sixdgs_gaussian_adam(n, n_coef, int(step), *[_p(params[k] if params[k].numel() else None) for k in FIT_GROUPS],
+                                           *[_p(t if t is not None and t.numel() else None) for t in g], _p(state["m"]), _p(state["v"]), rates,
+                                           float(beta1), float(beta2), float(eps), _p(instances), int(max_instances), _p(status), _stream()),
+          "gaussian_adam")
+
+
+@_on_device
+def opacity_reset(opacity: torch.Tensor, m_opacity: Optional[torch.Tensor] = None, v_opacity: Optional[torch.Tensor] = None, *,
+                  ceiling: float = 0.01, opacity_is_logit: bool = True) -> None:
+    """The reference's reset_opacity, IN PLACE (sixdgs_opacity_reset in include/sixdgs.h): opacity [N] or [N,1] becomes
+    min(sigmoid(x), ceiling) in the form it came in, and m_opacity, v_opacity -- the opacity slices of Adam's m and v -- become zero."""
+    if not (0.0 < float(ceiling) < 1.0):
+        raise ValueError(f"ceiling must be in (0, 1) (got {ceiling})")
+    for name, t in (("opacity", opacity), ("m_opacity", m_opacity), ("v_opacity", v_opacity)):
+        if t is None and name != "opacity":
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != opacity.numel():
+            raise ValueError(f"{name} must be a contiguous float32 tensor of opacity's size")
+    _need_gpu(opacity, m_opacity, v_opacity)
+    check(_lib.load().sixdgs_opacity_reset(_p(opacity), opacity.numel(), int(bool(opacity_is_logit)), _p(m_opacity), _p(v_opacity),
+                                           float(ceiling), _stream()), "opacity_reset")
+
+
+def fit_scene_workspace_bytes(n: int, n_coef: int, batch: int, width: int, height: int, max_instances: int) -> int:
+    return int(_lib.load().sixdgs_fit_scene_workspace_bytes(int(n), int(n_coef), int(batch), int(width), int(height), int(max_instances)))
+
+
+@_on_device
+def fit_scene_raw(params: dict, cams: torch.Tensor, width: int, height: int, target: torch.Tensor, *, views, lrs, sh_degrees, resets=None,
+                  groups=FIT_GROUPS, lambda_dssim: float = 0.2, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-15,
+                  reset_ceiling: float = 0.01, scale_modifier: float = 1.0, background=(1.0, 1.0, 1.0), scale_is_log: bool = True,
+                  opacity_is_logit: bool = True, max_instances: Optional[int] = None, retry: bool = True) -> dict:
+    """Fit the six arrays of `params` (a dict by FIT_GROUPS' names, UPDATED IN PLACE) to posed views as ONE library call
+    (sixdgs_fit_scene in include/sixdgs.h): per step a render of the step's views, the loss, the backward, one Adam step and -- where
+    asked -- the opacity reset, enqueued without a host read.  cams [V,16]; target fp32 [V,height,width,3|4] or uint8 [V,height,width,3];
+    views int [steps,batch] (indices into cams, duplicates allowed), lrs [steps,6] in FIT_GROUPS' order, sh_degrees [steps],
+    resets [steps] (None: never); groups: the names that move (the others stay bit for bit and get no gradient).
+    Returns a dict: history [steps,batch], m, v, status (int32 [1]; bit 0: a gradient entry was not finite and was left out, bit 1: the
+    instance capacity was too small), instances_needed (int) and max_instances (int: the capacity of the run returned).  The call
+    runs with raster_instances_estimate's capacity (or max_instances), reads status and instances_needed once at the end, and -- with
+    retry -- on bit 1 puts back the copy of the scene it took before the call and runs once more with 5/4 of the needed capacity."""
+    n, n_coef = _fit_params(params)
+    lam = float(lambda_dssim)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_dssim must be in [0, 1] (got {lambda_dssim})")
+    _check_fit_hyper(beta1, beta2, eps)
+    if not (0.0 < float(reset_ceiling) < 1.0):
+        raise ValueError(f"reset_ceiling must be in (0, 1) (got {reset_ceiling})")
+    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
+        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
+    if int(width) < 1 or int(height) < 1:
+        raise ValueError(f"width and height must be positive (got {width} x {height})")
+    if len(background) != 3:
+        raise ValueError("background must have 3 entries")
+    if max_instances is not None and not 1 <= int(max_instances) <= RASTER_MAX_INSTANCES:
+        raise ValueError(f"max_instances must be in [1, 2^31) (got {max_instances})")
+    groups = tuple(groups)
+    if not groups or any(k not in FIT_GROUPS for k in groups) or len(set(groups)) != len(groups):
+        raise ValueError(f"groups must name some of {FIT_GROUPS}, each once (got {groups})")
+    if not torch.is_tensor(cams) or cams.dim() != 2 or cams.shape[1] != 16 or cams.shape[0] < 1:
+        raise ValueError("cams must be a [views,16] tensor of at least one view")
+    cams = _f32(cams)
+    n_views, width, height = cams.shape[0], int(width), int(height)
+    view_t = torch.as_tensor(views).detach().cpu()
+    if view_t.dim() != 2 or view_t.shape[0] < 1 or view_t.shape[1] < 1 or view_t.dtype.is_floating_point or view_t.dtype == torch.bool:
+        raise ValueError("views must be an integer [steps,batch] array")
+    steps, batch = int(view_t.shape[0]), int(view_t.shape[1])
+    if int(view_t.min()) < 0 or int(view_t.max()) >= n_views:
+        raise ValueError(f"views must index the {n_views} cameras")
+    view_t = view_t.to(torch.int32).contiguous()
+    lr_t = torch.as_tensor(lrs, dtype=torch.float64).detach().cpu()
+    if tuple(lr_t.shape) != (steps, len(FIT_GROUPS)) or not bool(torch.isfinite(lr_t).all()) or bool((lr_t < 0).any()):
+        raise ValueError(f"lrs must be [{steps},{len(FIT_GROUPS)}] non-negative finite rates")
+    lr_t = lr_t.to(torch.float32).contiguous()
+    deg_t = torch.as_tensor(sh_degrees).detach().cpu()
+    if tuple(deg_t.shape) != (steps,) or deg_t.dtype.is_floating_point or int(deg_t.min()) < 0 or (int(deg_t.max()) + 1) ** 2 > n_coef:
+        raise ValueError(f"sh_degrees must be [{steps}] integers in [0, the degree {n_coef} coefficients allow]")
+    deg_t = deg_t.to(torch.int32).contiguous()
+    reset_t = torch.zeros(steps, dtype=torch.uint8) if resets is None else torch.as_tensor(resets).detach().cpu().to(torch.bool).to(torch.uint8).contiguous()
+    if tuple(reset_t.shape) != (steps,):
+        raise ValueError(f"resets must be [{steps}] flags")
+    if bool(reset_t.any()) and not opacity_is_logit:
+        raise ValueError("an opacity reset needs opacity_is_logit")
+    if not torch.is_tensor(target) or target.dim() != 4 or tuple(target.shape[:3]) != (n_views, height, width):
+        raise ValueError(f"target must be a [{n_views},{height},{width},3|4] tensor")
+    if target.dtype == torch.uint8:
+        if target.shape[3] != 3:
+            raise ValueError("a uint8 target must have 3 channels")
+    elif target.dtype != torch.float32 or target.shape[3] not in (3, 4):
+        raise ValueError("target must be float32 with 3 or 4 channels, or uint8 with 3")
+    if not target.is_contiguous():
+        raise ValueError("target must be contiguous")
+    target = target.detach()
+    arrays = [params[k] for k in FIT_GROUPS]
+    _need_gpu(*arrays, cams, target)
+    lib = _lib.load()
+    dev = cams.device
+    bg = torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
+    size = n * (11 + 3 * n_coef)
+    out = {"history": torch.empty(steps, batch, device=dev), "m": torch.empty(size, device=dev), "v": torch.empty(size, device=dev),
+           "status": torch.empty(1, dtype=torch.int32, device=dev)}
+    needed_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    mask = sum(1 << FIT_GROUPS.index(k) for k in groups)
+    capacity = int(max_instances) if max_instances is not None else raster_instances_estimate(n, batch)
+    saved = [t.clone() for t in arrays] if retry else None      # a run that overflowed has moved the scene up to that step
+    needed = 0
+    for attempt in range(2):
+        need = lib.sixdgs_fit_scene_workspace_bytes(n, n_coef, batch, width, height, capacity)
+        if need == 0:
+            raise ValueError(f"sizes outside the rasteriser's limits (n {n}, batch {batch}, {width} x {height}, instances {capacity})")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        p = params
+        check(lib.sixdgs_fit_scene(_p(p["xyz"]), _p(p["scale"]), int(scale_is_log), _p(p["rot"]), _p(p["opacity"]), int(opacity_is_logit),
+                                   _p(p["f_dc"]), _p(p["f_rest"] if n_coef > 1 else None), n_coef, n, _p(cams), n_views, width, height,
+                                   float(scale_modifier), _p(bg), _p(target), int(target.dtype == torch.uint8), int(target.shape[3]), lam, steps,
+                                   batch, C.c_void_p(view_t.data_ptr()), C.c_void_p(lr_t.data_ptr()), C.c_void_p(deg_t.data_ptr()),
+                                   C.c_void_p(reset_t.data_ptr()), mask, float(beta1), float(beta2), float(eps), float(reset_ceiling), capacity,
+                                   _p(out["m"]), _p(out["v"]), _p(out["history"]), _p(out["status"]), _p(needed_t), _p(ws), need, _stream()),
+              "fit_scene")
+        # the one host read of the call: the status word and the largest instance count seen
+        flags = torch.cat([out["status"].to(torch.int64), needed_t]).cpu()
+        needed = int(flags[1])
+        if not retry or not int(flags[0]) & FIT_STATUS_CAPACITY:
+            break
+        if attempt == 1 or needed > RASTER_MAX_INSTANCES:
+            raise RuntimeError(f"6dgs_amd: fit_scene still needs {needed} tile instances after {attempt + 1} runs (limit 2^31 - 1): "
+                               "fit fewer views at once")
+        for t, s in zip(arrays, saved):
+            t.copy_(s)
+        capacity = min(max(needed + needed // 4, 1), RASTER_MAX_INSTANCES)
+    out["instances_needed"] = needed
+    out["max_instances"] = capacity
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # scorer
 # ---------------------------------------------------------------------------------------------
 class PackedWeights:

@@ -415,6 +415,91 @@ int sixdgs_refine_poses(const float* xyz, const float* scale, int scale_is_log, 
                         size_t ws_bytes, sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Adam over a scene's Gaussians and the opacity reset (additive in ABI 10): the optimiser's side of fitting a FIXED set of Gaussians
+ * to posed views (the reference's train.py:94-122 and scene/gaussian_model.py:230-282 without densification: n never changes, no
+ * clone, split or prune, and none of their statistics).  All arithmetic in fp32, no contraction into fused multiply-adds; one owner
+ * per output, no floating-point atomics, the same bytes on every call.
+ *
+ * GROUPS.  Six, in this order everywhere: xyz [n,3], f_dc [n,1,3], f_rest [n,n_coef-1,3], opacity [n], scale [n,3], rot [n,4]:
+ * 11 + 3 n_coef floats per Gaussian.  m and v are each ONE buffer of n (11 + 3 n_coef) floats, group after group in that order, so the
+ * slices start at 0, 3n, 6n, 3n (n_coef + 1), 3n (n_coef + 1) + n and 3n (n_coef + 2) + n floats.
+ *
+ * sixdgs_gaussian_adam updates the six parameter arrays in place from their six gradient arrays: Adam's step t = step + 1 (the ADAM
+ * of sixdgs_pose_step, with the group's rate), per entry with gradient g:
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) (g g);  p = p - (lr[k] / c1) (m / (sqrt(v) / c2 + eps)),
+ *   c1 = 1 - beta1^t and c2 = sqrt(1 - beta2^t) formed by the host in double from the float arguments and rounded to float;
+ *   lr [6] is a HOST array, read at the call.
+ * Rules:
+ *   1. a group whose gradient pointer is NULL is frozen: its parameters and its slice of m and v are not touched, bit for bit (its
+ *      parameter pointer may then be NULL as well); with n_coef == 1 the f_rest group is empty and both its pointers are ignored;
+ *   2. lr[k] == 0 is legal and still updates m and v, as torch.optim.Adam does;
+ *   3. an entry whose gradient is not finite keeps p, m and v, and bit 0 of status[0] is set;
+ *   4. with count = *instances (instances may be NULL: no check): if count > max_instances the step changes nothing at all and sets
+ *      bit 1 of status[0] -- the gradients of an overflowed rasteriser call are unspecified;
+ *   5. status[0] is read on entry: once bit 1 is set, later calls change nothing.  The caller starts status[0] as 0.
+ * Bits are set with an integer atomic OR.  One launch covers all groups: workgroups walk a flat index over the groups' entries, with
+ * 16-byte accesses where a group's four pointers (parameter, gradient, its m and v slices) are all 16-byte aligned and 4-byte accesses
+ * otherwise; the arithmetic is per entry, so the bits do not depend on the alignment.
+ * Limits: n < 2^31, 1 <= n_coef <= 16, 0 <= step, lr[k] >= 0 finite, beta1, beta2 in [0, 1), eps >= 0 finite, 1 <= max_instances < 2^31.
+ * SIXDGS_E_BADARG without a launch for argument errors: a NULL lr, m, v or status, a NULL parameter pointer whose gradient pointer is
+ * not NULL (a NULL f_rest with n_coef > 1 when its gradient is given included), m == v, a misaligned array (4 bytes; instances 8).
+ * n == 0 returns 0.
+ *
+ * sixdgs_opacity_reset is the reference's reset_opacity on the array and on the optimiser's state: per Gaussian, with x its opacity,
+ *   a = 1 / (1 + exp(-x)) when opacity_is_logit != 0, x otherwise;  o = min(a, ceiling);
+ *   opacity = log(o / (1 - o)) when opacity_is_logit != 0, o otherwise;  m_opacity = v_opacity = 0
+ * (m_opacity, v_opacity: the opacity slices of m and v, each may be NULL).  ceiling in (0, 1); n == 0 returns 0; SIXDGS_E_BADARG
+ * without a launch otherwise. */
+int sixdgs_gaussian_adam(int64_t n, int n_coef, int step, float* xyz, float* f_dc, float* f_rest, float* opacity, float* scale, float* rot,
+                         const float* d_xyz, const float* d_f_dc, const float* d_f_rest, const float* d_opacity, const float* d_scale,
+                         const float* d_rot, float* m, float* v, const float* lr /*[6] host*/, float beta1, float beta2, float eps,
+                         const int64_t* instances /*[1] device or NULL*/, int64_t max_instances, int32_t* status /*[1] device*/,
+                         sixdgs_stream_t stream);
+int sixdgs_opacity_reset(float* opacity /*[n]*/, int64_t n, int opacity_is_logit, float* m_opacity /*[n] or NULL*/,
+                         float* v_opacity /*[n] or NULL*/, float ceiling, sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fitting a scene's Gaussians to posed views as one call (additive in ABI 10).  The scene arrays are MUTABLE and updated in place; n is
+ * fixed for the whole fit (no densification).  The call first zeroes m, v, status[0] and instances_needed[0], then for
+ * s = 0 .. steps - 1 enqueues on `stream`, in this order and through the entry points above as they are:
+ *   1. the step's views h_view[s][0 .. batch): with batch == 1 pointer offsets into cams and the target, no copy; otherwise
+ *      device-to-device copies of the batch's camera rows and target views into the workspace, in slot order (duplicates allowed);
+ *   2. sixdgs_raster_views at sh_degree h_sh_degree[s] (float image only; the instance count is left on the device);
+ *   3. sixdgs_photometric_loss with the gradient, grad_loss NULL: the objective is the sum of the batch's per-view losses;
+ *   4. sixdgs_raster_views_backward with exactly the outputs of the groups set in group_mask (bit k = group k in the order xyz, f_dc,
+ *      f_rest, opacity, scale, rot) and no d_cams;
+ *   5. history[s][b] = the loss of slot b; instances_needed[0] = max(instances_needed[0], count).  If count > max_instances, bit 1 of
+ *      status[0] is set; while bit 1 is set the row is NaN instead;
+ *   6. sixdgs_gaussian_adam with step s, the rates h_lr[s][6] and that count; a group cleared in group_mask is frozen;
+ *   7. when h_reset[s] != 0: sixdgs_opacity_reset with reset_ceiling on the array and the opacity slices of m and v, skipped once bit 1
+ *      is set (it runs whether or not the opacity group is in group_mask).
+ * h_view [steps][batch] int32, h_lr [steps][6], h_sh_degree [steps] int32 and h_reset [steps] uint8 are HOST arrays, read at the call.
+ * The call makes no host synchronisation, no device-to-host copy and no allocation; the library stays stateless; when it returns, the
+ * work is enqueued.  SAME INPUT, SAME BYTES.  Scene arrays, flags, scale_modifier and background (device [3]) as sixdgs_raster_views
+ * takes them; cams [views][16]; the target in the three forms sixdgs_photometric_loss takes, views images of width x height.
+ * Outputs (device): the scene arrays; m, v (caller-owned, n (11 + 3 n_coef) floats each); history [steps][batch]; status [1] (bit 0: a
+ * gradient entry was not finite and was left out, bit 1: capacity); instances_needed [1] = the largest instance count seen.  When
+ * max_instances was too small at some step, that step and all later ones change nothing and their history rows are NaN: the scene, m
+ * and v are as they were after the last good step; call again, from the scene as it was before the call, with
+ * max_instances >= instances_needed[0].
+ * Limits are the parts': the rasteriser's sizes with views = batch, 1 <= views <= 65535, 1 <= batch, lambda in [0, 1], 1 <= steps, the
+ * limits of sixdgs_gaussian_adam and sixdgs_opacity_reset, 0 < group_mask < 64, h_sh_degree[s] in [0, 3] with
+ * (h_sh_degree[s] + 1)^2 <= n_coef.  SIXDGS_E_BADARG for argument errors -- a view index outside [0, views) and a reset asked for
+ * without opacity_is_logit included --, SIXDGS_E_WORKSPACE for too small a workspace, both without touching a GPU.
+ * sixdgs_fit_scene_workspace_bytes is answered without a GPU and is 0 outside the limits: the three parts' workspaces at `batch` views
+ * (the loss's with the gradient), two float images of batch x height x width x 4, the gathered camera rows, the gathered targets
+ * (reserved for the widest form, 16 B per pixel), the losses, the count, and the six gradient arrays (n (11 + 3 n_coef) floats), each
+ * piece rounded up to 256 B. */
+size_t sixdgs_fit_scene_workspace_bytes(int64_t n, int n_coef, int batch, int width, int height, int64_t max_instances);
+int sixdgs_fit_scene(float* xyz, float* scale, int scale_is_log, float* rot, float* opacity, int opacity_is_logit, float* f_dc, float* f_rest,
+                     int n_coef, int64_t n, const float* cams /*[views][16]*/, int views, int width, int height, float scale_modifier,
+                     const float* background /*[3] device*/, const void* target, int target_is_u8, int target_stride, float lambda, int steps,
+                     int batch, const int32_t* h_view /*[steps][batch] host*/, const float* h_lr /*[steps][6] host*/,
+                     const int32_t* h_sh_degree /*[steps] host*/, const uint8_t* h_reset /*[steps] host*/, int group_mask, float beta1,
+                     float beta2, float eps, float reset_ceiling, int64_t max_instances, float* m, float* v, float* history /*[steps][batch]*/,
+                     int32_t* status /*[1]*/, int64_t* instances_needed /*[1]*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scorer, scene side (once per scene): ray MLP + k_proj -> key cache
  * replaces RayPreprocessor.forward (ray_preprocessor.py:36-46) + k_proj (our_multihead_attention.py:74)
  * ------------------------------------------------------------------------------------------- */

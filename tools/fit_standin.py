@@ -1,0 +1,92 @@
+"""Fit a perturbed stand-in scene back to views of the scene that rendered them, with both backends of fit.fit_scene.
+
+    python tools/fit_standin.py [--gaussians 5000] [--size 112] [--views 8] [--steps 60] [--batch 1] [--rounds 3]
+
+A stand-in scene (synthetic.make_scene) renders `views` views with renderer="raster"; a copy is perturbed -- colours, opacity logits,
+positions and log-scales by Gaussian noise of the given standard deviations -- and fitted to the views.  In one process the two arms
+alternate `rounds` times after one warm-up call each, the arrangement of tools/time_refine.py: backend="torch" (autograd and
+torch.optim.Adam around the kernels) and backend="fused" (one sixdgs_fit_scene call).  HIP events around the whole fit_scene call --
+the target's preparation, the scene's copy and the final read included -- divided by the steps.  Prints ms per step, the loss
+histories' largest difference, and the parameters' RMS distance from the rendering scene before and after; asserts nothing."""
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+os.environ.setdefault("SIXDGS_RANDOM_BACKBONE", "1")
+
+ATTR = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scale": "_scaling", "rot": "_rotation"}
+
+
+def perturbed(pkg, scene, sizes, seed):
+    gen = torch.Generator().manual_seed(seed)
+    out = pkg.GaussianScene(scene.max_sh_degree)
+    for k, a in ATTR.items():
+        t = getattr(scene, a).clone()
+        if sizes.get(k, 0.0) > 0.0:
+            t += (sizes[k] * torch.randn(t.shape, generator=gen)).to(t.device)
+        setattr(out, a, t)
+    return out
+
+
+def rms(a, b):
+    return {k: float((getattr(a, attr) - getattr(b, attr)).pow(2).mean().sqrt()) for k, attr in ATTR.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--gaussians", type=int, default=5000)
+    ap.add_argument("--seed", type=int, default=11)
+    ap.add_argument("--size", type=int, default=112)
+    ap.add_argument("--views", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=60)
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--colour", type=float, default=0.05, help="noise on f_dc")
+    ap.add_argument("--opacity", type=float, default=0.5, help="noise on the opacity logits")
+    ap.add_argument("--position", type=float, default=0.002, help="noise on xyz")
+    ap.add_argument("--log_scale", type=float, default=0.05, help="noise on the log-scales")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("fit_standin needs a GPU")
+    import train_standin as ts
+    pkg, _, _, test = ts.modules()
+    fit = importlib.import_module("6dgs_amd.fit")
+    scene, _, held = ts.build_standin(args.gaussians, args.seed, 2, args.views, args.size, renderer="raster")
+    c2w, Ks = zip(*[test.gt_pose_and_intrinsics(c, "cpu") for c in held])
+    c2w, K, images = torch.stack(c2w), torch.stack(Ks), [c.image for c in held]
+    start = perturbed(pkg, scene, {"f_dc": args.colour, "opacity": args.opacity, "xyz": args.position, "scale": args.log_scale}, args.seed)
+    print(f"{args.gaussians} Gaussians, {args.views} views of {args.size} x {args.size}, {args.steps} steps of {args.batch}, {args.rounds} rounds")
+    ms, out = {"torch": [], "fused": []}, {}
+    for rnd in range(args.rounds + 1):                    # round 0 warms both arms up
+        for backend in ("torch", "fused"):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            out[backend] = fit.fit_scene(start, images, c2w, K, steps=args.steps, batch=args.batch, backend=backend)
+            b.record()
+            torch.cuda.synchronize()
+            if rnd:
+                ms[backend].append(a.elapsed_time(b) / args.steps)
+    for backend, v in ms.items():
+        print(f"{backend}: ms per step, each round: {', '.join(f'{x:.3f}' for x in v)}; median {np.median(v):.3f}, min {min(v):.3f}, max {max(v):.3f}")
+    print(f"fused / torch (medians): {np.median(ms['fused']) / np.median(ms['torch']):.3f}")
+    (st, rt), (sf, rf) = out["torch"], out["fused"]
+    tail = min(3 * args.views // args.batch, args.steps)
+    print(f"first loss torch {float(rt['loss_history'][0].mean()):.5f} (equal bits: {torch.equal(rt['loss_history'][0], rf['loss_history'][0])}); "
+          f"mean of the last {tail} steps torch {float(rt['loss_history'][-tail:].mean()):.5f}, fused {float(rf['loss_history'][-tail:].mean()):.5f}; "
+          f"max |history difference| {float((rt['loss_history'] - rf['loss_history']).abs().max()):.3e}; status {int(rf['status'])}")
+    before, after_t, after_f = rms(start, scene), rms(st, scene), rms(sf, scene)
+    for k in ATTR:
+        print(f"  rms distance from the rendering scene, {k:8s}: before {before[k]:.3e}, after torch {after_t[k]:.3e}, fused {after_f[k]:.3e}")
+
+
+if __name__ == "__main__":
+    main()
