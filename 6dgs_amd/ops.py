@@ -1024,6 +1024,13 @@ def linear(x, w, b=None, relu: bool = False, mma_mode: Optional[int] = None, spl
 TOK_ATTENTION_MAX_TOKENS = 288
 
 
+def _tok_out_ok(y: torch.Tensor, m: int, n: int, what: str) -> None:
+    """The output of a ViT stage kernel: the caller's `out` is written as it lies (any row stride the kernel accepts), so its shape is checked here --
+    the kernels store m rows of n floats whatever the tensor holds."""
+    if y.dtype != torch.float32 or tuple(y.shape) != (m, n) or (n > 1 and y.stride(1) != 1) or not y.is_cuda:
+        raise RuntimeError(f"6dgs_amd: {what} needs a float32 GPU output [{m}, {n}] with unit column stride, got {y.dtype} {tuple(y.shape)} strides {tuple(y.stride())}")
+
+
 @_on_device
 def tok_attention(qkv: torch.Tensor, images: int, tokens: int, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(q k^T / 8) v per image and head on the QKV product's output [images * tokens, 3 * heads * 64] as it lies (q | k | v, head h at columns
@@ -1033,6 +1040,7 @@ def tok_attention(qkv: torch.Tensor, images: int, tokens: int, heads: int, out: 
         raise RuntimeError(f"6dgs_amd: tok_attention needs float32 qkv [{images * tokens}, {3 * heads * 64}], got {qkv.dtype} {tuple(qkv.shape)}")
     _need_gpu(qkv)
     y = out if out is not None else torch.empty(images * tokens, heads * 64, device=qkv.device)
+    _tok_out_ok(y, images * tokens, heads * 64, "tok_attention")
     check(_lib.load().sixdgs_tok_attention(_p(qkv), qkv.stride(0), int(images), int(tokens), int(heads), _p(y), y.stride(0), _stream()), "tok_attention")
     return y
 
@@ -1173,7 +1181,15 @@ def tok_linear(x: torch.Tensor, w, b: Optional[torch.Tensor] = None, *, ln=None,
         a_mode, ln_w, ln_b, eps = TOK_A_LAYERNORM, _f32(ln[0]), _f32(ln[1]), float(ln[2])
     m = x.shape[0]
     y = out if out is not None else torch.empty(m, n, device=x.device)
-    res = _f32(residual) if residual is not None else None
+    _tok_out_ok(y, m, n, "tok_linear")
+    res = None
+    if residual is not None:
+        if tuple(residual.shape) != (m, n):
+            raise RuntimeError(f"6dgs_amd: tok_linear needs a residual [{m}, {n}], got {tuple(residual.shape)}")
+        res = residual.detach()
+        # a row-strided view (ldr > n) is read where it lies, like x: a copy here would also turn `out is residual` into an out-of-place call
+        if res.dtype != torch.float32 or res.stride(1) != 1 or res.stride(0) % 4 != 0 or res.data_ptr() % 16 != 0:
+            res = _f32(res)
     check(_lib.load().sixdgs_tok_linear(_p(x), m, k, x.stride(0), a_mode, _p(ln_w), _p(ln_b), eps, _p(tw.planes), _p(tw.inv_scale), _p(b), n, int(epilogue),
                                         _p(res), res.stride(0) if res is not None else 0, _p(_f32(gamma)) if gamma is not None else None, _p(y), y.stride(0),
                                         _stream()), "tok_linear")

@@ -586,9 +586,20 @@ int sixdgs_linear_splitk(const float* x, int64_t m, int k, int64_t ldx, const fl
  *   a_mode   SIXDGS_TOK_A_PLAIN  x [m][ldx];
  *            SIXDGS_TOK_A_LAYERNORM  LayerNorm(x; ln_weight, ln_bias, ln_eps) over the k = 384 columns in front of the product (torch.nn.LayerNorm,
  *                                dinov2 block.norm1 / norm2);
- *   epilogue SIXDGS_TOK_EPI_BIAS  y [m][ldy] = acc + bias;   SIXDGS_TOK_EPI_GELU  gelu(acc + bias), erf form (mlp.fc1 + act; erf to 1.5e-7);
+ *   epilogue SIXDGS_TOK_EPI_BIAS  y [m][ldy] = acc + bias;   SIXDGS_TOK_EPI_GELU  gelu(acc + bias), erf form (mlp.fc1 + act; erf to 4.1e-7:
+ *                                Abramowitz & Stegun 7.1.26's 1.5e-7 plus its fp32 evaluation with the hardware's reciprocal and exp2; measured 3.3e-7);
  *            SIXDGS_TOK_EPI_RESID  residual [m][ldr] + gamma[n] * (acc + bias) (x + ls(branch(x)): attn.proj / mlp.fc2, LayerScale gamma or NULL = 1;
- *                                y may be the residual buffer itself). */
+ *                                y may be the residual buffer itself).
+ * Pinned against fp64, element by element (tests/vit_stage_reference.py; u = 2^-23; measured figures in profiles/vit_stage_edges.md):
+ *   v = prologue(x) . w^T + bias:  |dv_ij| <= 4e-7 (sum_k |xh_ik| |w_jk| + |bias_j|) + u |v_ij| + 2^-125 (sum_k |w_jk| + 1), xh = x or LayerNorm(x);
+ *   LayerNorm prologue:            + 0.5 u (1 + max_k |x_ik| / sqrt(var_i + eps)) sum_k |ln_weight_k| |w_jk|;
+ *   GELU:                          |dy| <= 1.13 |dv| + 0.5 |v| 4.1e-7 + u |y|;  gelu(-40) = -0, never NaN;
+ *   residual:                      |dy| <= |gamma_j| |dv| + u (|residual_ij| + |gamma_j v_ij|).
+ *   (the 2^-125 term: a row's power-of-two scale is clamped to 2^+-100, so rows whose largest magnitude lies below 2^-113 keep an absolute grid.)
+ * Rows never mix: row i of y depends on row i of x (and of residual), the weights and a fixed order of operations alone -- the same bits whatever m,
+ * ldx, ldy, ldr, the row's place in its 64-row tile, the number of feature tiles a workgroup walks, in place or not; a NaN / Inf row of x makes its own
+ * output row non-finite and no other.  Rows of x, residual and y beyond m are neither read nor written, nor are columns beyond k / n.  An all-zero row of
+ * x gives exactly bias (plain prologue, bias epilogue) or the product of ln_bias (LayerNorm); an all-zero row of w gives exactly bias_j before the epilogue. */
 #define SIXDGS_TOK_A_PLAIN 0
 #define SIXDGS_TOK_A_LAYERNORM 1
 #define SIXDGS_TOK_EPI_BIAS 0
@@ -602,7 +613,12 @@ int sixdgs_tok_linear(const float* x, int64_t m, int k, int64_t ldx, int a_mode,
 
 /* The attention of a ViT block (dinov2 Attention.forward: softmax(q k^T / sqrt(64)) v per image and head) on the QKV product's output as it lies:
  * qkv [images * tokens][ldq] = q | k | v, each heads * 64 wide, head h at columns h * 64; y [images * tokens][ldy], head h at columns h * 64 (what
- * attn.proj reads).  Head dimension 64, tokens <= 288 (SIXDGS_E_UNSUPPORTED beyond: the caller keeps its own attention); fp32-class results. */
+ * attn.proj reads).  Head dimension 64, tokens <= 288 (SIXDGS_E_UNSUPPORTED beyond: the caller keeps its own attention); fp32-class results.
+ * Pinned against fp64 per (image, head, query) (tests/vit_stage_reference.py): |dy_qd| <= (8e-7 Lambda_q + 4e-7) s_q, Lambda_q = max_key sum_d |q_d| |k_d| / 8,
+ * s_q = sum_key p_key max_d |v_key,d|.  Images and heads never mix: the output of (image, head) depends on that image's rows and that head's 3 x 64 columns
+ * alone -- the same bits whatever the batch, the strides and the number of query groups the launcher chooses; NaN in one image or one head's columns stays
+ * there.  Rows of qkv beyond images * tokens and columns beyond 3 * heads * 64 are not read.  K = 0 for a head (scale 0) gives the mean of the head's V rows
+ * over exactly `tokens` keys; V = 0 gives exactly 0. */
 int sixdgs_tok_attention(const float* qkv, int64_t ldq, int images, int tokens, int heads, float* y, int64_t ldy, sixdgs_stream_t stream);
 
 /* a22 (camera_direction_network.py:29-36, the valid k x k convolutions of the camera-up CNN) as GEMMs: the im2col matrix of a whole batch in one
