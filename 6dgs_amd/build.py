@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "lib6dgs_hip.so")
 HOSTCHECK = os.path.join(CSRC, "libsixdgs_hostcheck.so")
 SOURCES = ["geometry.hip", "gemm.hip", "dense.hip", "score.hip", "score_bwd.hip", "pose.hip", "pose_consensus.hip", "vit.hip", "splat.hip", "raster.hip", "photometric.hip", "refine.hip", "fit.hip"]
-HEADERS = ["common.h", "device_math.h", "gemm_kernel.h", "dense.h", os.path.join("..", "..", "include", "sixdgs.h"), "dense_layout.h", "sweep_plan.h", "sweep_layout.h", "pose_step.h", "adam_step.h"]
+HEADERS = ["common.h", "device_math.h", "gemm_kernel.h", "dense.h", os.path.join("..", "..", "include", "sixdgs.h"), "dense_layout.h", "sweep_plan.h", "sweep_layout.h", "pose_step.h", "adam_step.h", "render_pass.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 FLAGS += os.environ.get("SIXDGS_EXTRA_FLAGS", "").split()       # developer builds (e.g. -DSDG_DENSE_PROF: tools/prof_dense.py)

@@ -20,6 +20,12 @@ static inline hipStream_t sdg_stream(sixdgs_stream_t s) { return (hipStream_t)s;
 static inline size_t sdg_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int64_t sdg_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// A workspace handed out front to back in 256-byte steps; total = the bytes taken so far.  A Layout derives from it and starts zeroed.
+struct SdgBump {
+  size_t total;
+  size_t take(size_t bytes) { const size_t at = total; total += sdg_align(bytes); return at; }
+};
+
 // ---- wave / block primitives (wave = 64 lanes on gfx950) ----------------------------------------
 __device__ __forceinline__ int sdg_lane() { return threadIdx.x & 63; }
 __device__ __forceinline__ int sdg_wave() { return threadIdx.x >> 6; }

@@ -5,17 +5,17 @@
 #include <math.h>
 
 #include "adam_step.h"
-#include "common.h"
+#include "render_pass.h"
 
 namespace {
 
 using namespace sdg;
+using namespace rp;
 
 constexpr int kBlock = 256;
 constexpr int kVec = 4;                      // floats per 16-byte access
 constexpr int kChunk = kBlock * kVec;        // entries a workgroup takes at a time
 constexpr int kMaxBlocks = 2048;             // 256 CUs x 8 workgroups; the rest of the chunks by grid stride
-constexpr int kMaxViews = 65535;
 
 // One parameter group of the step.  count = 0: frozen, it owns no chunk.
 struct Group {
@@ -124,12 +124,8 @@ __global__ __launch_bounds__(64) void k_fit_record(const float* __restrict__ los
   if (b < batch) history_row[b] = over ? NAN : loss[b];
 }
 
-bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-bool hyper_ok(float beta1, float beta2, float eps) {
-  return beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && eps < INFINITY;
-}
 bool lr_ok(const float* lr) {
   if (!lr) return false;
   for (int k = 0; k < ga::kGroups; ++k)
@@ -148,34 +144,16 @@ int launch_reset(float* opacity, int64_t n, int is_logit, float* m, float* v, fl
   return 0;
 }
 
-struct Layout {
-  size_t fwd, bwd, photo, image, grad, rows, target, loss, count, g[ga::kGroups], total;
-  size_t fwd_bytes, bwd_bytes, photo_bytes;
+struct Layout : PassLayout {
+  size_t target, g[ga::kGroups];
 };
 
-// 0 total = outside the limits (the rasteriser's: its workspace is never 0 inside them)
+// 0 total = outside the limits
 Layout layout(int64_t n, int n_coef, int batch, int width, int height, int64_t max_instances) {
   Layout L = {};
-  if (n_coef < 1 || n_coef > 16 || batch < 1) return L;
-  L.fwd_bytes = sixdgs_raster_views_workspace_bytes(n, batch, width, height, max_instances);
-  L.bwd_bytes = sixdgs_raster_views_backward_workspace_bytes(n, batch, width, height, max_instances);
-  if (L.fwd_bytes == 0 || L.bwd_bytes == 0) return L;
-  L.photo_bytes = sixdgs_photometric_loss_workspace_bytes(batch, width, height, 1);
-  if (L.photo_bytes == 0) return L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += sdg_align(bytes); return at; };
-  const size_t px = (size_t)batch * (size_t)height * (size_t)width;
-  L.fwd = take(L.fwd_bytes);
-  L.bwd = take(L.bwd_bytes);
-  L.photo = take(L.photo_bytes);
-  L.image = take(px * 4 * sizeof(float));
-  L.grad = take(px * 4 * sizeof(float));
-  L.rows = take((size_t)batch * 16 * sizeof(float));
-  L.target = take(px * 4 * sizeof(float));      // the widest of the three target forms
-  L.loss = take((size_t)batch * sizeof(float));
-  L.count = take(sizeof(int64_t));
-  for (int k = 0; k < ga::kGroups; ++k) L.g[k] = take((size_t)n * ga::group_width(k, n_coef) * sizeof(float));
-  L.total = o;
+  if (n_coef < 1 || n_coef > 16 || batch < 1 || !pass_layout(L, n, batch, width, height, max_instances)) return L;
+  L.target = L.take((size_t)batch * (size_t)height * (size_t)width * 4 * sizeof(float));      // the widest of the three target forms
+  for (int k = 0; k < ga::kGroups; ++k) L.g[k] = L.take((size_t)n * ga::group_width(k, n_coef) * sizeof(float));
   return L;
 }
 
@@ -247,15 +225,12 @@ int sixdgs_fit_scene(float* xyz, float* scale, int scale_is_log, float* rot, flo
                      float reset_ceiling, int64_t max_instances, float* m, float* v, float* history, int32_t* status, int64_t* instances_needed,
                      void* ws, size_t ws_bytes, sixdgs_stream_t stream) {
   const Layout L = layout(n, n_coef, batch, width, height, max_instances);
+  const Scene S = {xyz, scale, rot, opacity, f_dc, f_rest, background, scale_is_log, opacity_is_logit, n_coef, n, scale_modifier};
+  Target T = {target, target_is_u8, target_stride};
   SDG_CHECK_ARG(L.total != 0);
   SDG_CHECK_ARG(views >= 1 && views <= kMaxViews);
-  SDG_CHECK_ARG(scale_modifier > 0.f && scale_modifier < INFINITY);
-  SDG_CHECK_ARG(scale_is_log == 0 || scale_is_log == 1);
-  SDG_CHECK_ARG(opacity_is_logit == 0 || opacity_is_logit == 1);
-  SDG_CHECK_ARG(target_is_u8 == 0 || target_is_u8 == 1);
-  SDG_CHECK_ARG(target_is_u8 ? target_stride == 3 : (target_stride == 3 || target_stride == 4));
-  SDG_CHECK_ARG(lambda >= 0.f && lambda <= 1.f);
-  SDG_CHECK_ARG(steps >= 1 && steps < INT32_MAX - 1);
+  SDG_CHECK_ARG((scale_is_log == 0 || scale_is_log == 1) && (opacity_is_logit == 0 || opacity_is_logit == 1));
+  SDG_CHECK_ARG(target_ok(T) && loop_ok(lambda, steps));
   SDG_CHECK_ARG(group_mask > 0 && group_mask < (1 << ga::kGroups));
   SDG_CHECK_ARG(hyper_ok(beta1, beta2, eps));
   SDG_CHECK_ARG(reset_ceiling > 0.f && reset_ceiling < 1.f);
@@ -263,21 +238,17 @@ int sixdgs_fit_scene(float* xyz, float* scale, int scale_is_log, float* rot, flo
   for (int s = 0; s < steps; ++s) {
     for (int b = 0; b < batch; ++b) SDG_CHECK_ARG(h_view[(size_t)s * batch + b] >= 0 && h_view[(size_t)s * batch + b] < views);
     SDG_CHECK_ARG(lr_ok(h_lr + (size_t)s * ga::kGroups));
-    const int d = h_sh_degree[s];
-    SDG_CHECK_ARG(d >= 0 && d <= 3 && (d + 1) * (d + 1) <= n_coef);
+    SDG_CHECK_ARG(scene_ok(S, h_sh_degree[s]));
     SDG_CHECK_ARG(h_reset[s] == 0 || opacity_is_logit);
   }
-  SDG_CHECK_ARG(cams && background && target && history && status && instances_needed);
-  SDG_CHECK_ARG(n == 0 || (xyz && scale && rot && opacity && f_dc && (n_coef == 1 || f_rest) && m && v && m != v));
+  SDG_CHECK_ARG(cams && scene_present(S) && target_present(T) && history && status && instances_needed);
+  SDG_CHECK_ARG(n == 0 || (m && v && m != v));
   SDG_CHECK_ARG(aligned4(xyz) && aligned4(scale) && aligned4(rot) && aligned4(opacity) && aligned4(f_dc) && aligned4(f_rest) && aligned4(cams) &&
-                (target_is_u8 || aligned4(target)) && aligned4(m) && aligned4(v) && aligned4(history) && aligned4(status) &&
-                ((uintptr_t)instances_needed & 7) == 0);
+                aligned4(m) && aligned4(v) && aligned4(history) && aligned4(status) && ((uintptr_t)instances_needed & 7) == 0);
   if (ws_bytes < L.total) return SIXDGS_E_WORKSPACE;
   SDG_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0);
   hipStream_t s = sdg_stream(stream);
   char* w = (char*)ws;
-  float* image = (float*)(w + L.image);
-  float* grad = (float*)(w + L.grad);
   float* rows = (float*)(w + L.rows);
   char* tgt = w + L.target;
   float* loss = (float*)(w + L.loss);
@@ -298,9 +269,9 @@ int sixdgs_fit_scene(float* xyz, float* scale, int scale_is_log, float* rot, flo
   const int64_t op_off = n * 3 * ((int64_t)n_coef + 1);      // the opacity slice of m and v: behind xyz, f_dc and f_rest
   for (int step = 0; step < steps; ++step) {
     const int32_t* view = h_view + (size_t)step * batch;
-    const float* step_rows = cams + 16 * (size_t)view[0];
-    const void* step_target = (const char*)target + view_bytes * (size_t)view[0];
-    if (batch > 1) {
+    const float* step_rows = batch > 1 ? rows : cams + 16 * (size_t)view[0];      // one view is read where it lies, more are gathered
+    T.data = batch > 1 ? tgt : (const char*)target + view_bytes * (size_t)view[0];
+    if (batch > 1)
       for (int b = 0; b < batch; ++b) {
         if ((e = hipMemcpyAsync(rows + 16 * (size_t)b, cams + 16 * (size_t)view[b], 16 * sizeof(float), hipMemcpyDeviceToDevice, s)) != hipSuccess)
           return (int)e;
@@ -308,20 +279,8 @@ int sixdgs_fit_scene(float* xyz, float* scale, int scale_is_log, float* rot, flo
                                 hipMemcpyDeviceToDevice, s)) != hipSuccess)
           return (int)e;
       }
-      step_rows = rows;
-      step_target = tgt;
-    }
-    const int deg = h_sh_degree[step];
-    int st = sixdgs_raster_views(xyz, scale, scale_is_log, rot, opacity, opacity_is_logit, f_dc, f_rest, deg, n_coef, n, step_rows, batch, width,
-                                 height, scale_modifier, background, image, nullptr, 3, nullptr, max_instances, count, w + L.fwd, L.fwd_bytes,
-                                 stream, nullptr);
-    if (st != 0) return st;
-    st = sixdgs_photometric_loss(image, 4, step_target, target_is_u8, target_stride, batch, width, height, lambda, nullptr, loss, nullptr, grad,
-                                 w + L.photo, L.photo_bytes, stream, nullptr);
-    if (st != 0) return st;
-    st = sixdgs_raster_views_backward(xyz, scale, scale_is_log, rot, opacity, opacity_is_logit, f_dc, f_rest, deg, n_coef, n, step_rows, batch,
-                                      width, height, scale_modifier, background, grad, max_instances, w + L.fwd, L.fwd_bytes, d[0], d[4], d[5],
-                                      d[3], d[1], d[2], nullptr, w + L.bwd, L.bwd_bytes, stream, nullptr);
+    int st = render_pass(S, h_sh_degree[step], step_rows, batch, width, height, T, lambda, max_instances, L, w, (float*)(w + L.grad), d[0],
+                             d[4], d[5], d[3], d[1], d[2], nullptr, stream);
     if (st != 0) return st;
     hipLaunchKernelGGL(k_fit_record, dim3((unsigned)sdg_cdiv(batch, 64)), dim3(64), 0, s, loss, batch, count, max_instances,
                        history + (size_t)step * batch, status, instances_needed);

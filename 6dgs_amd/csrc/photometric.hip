@@ -33,17 +33,14 @@ bool sizes_ok(int views, int width, int height) {
   return (int64_t)views * sdg_cdiv(width, kTile) * sdg_cdiv(height, kTile) < ((int64_t)1 << 31);
 }
 
-struct Layout {
-  size_t part, maps, total;
+struct Layout : SdgBump {
+  size_t part, maps;
 };
 
 Layout layout(int views, int width, int height, int want_grad) {
-  Layout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += sdg_align(bytes); return at; };
-  L.part = take((size_t)views * (size_t)(sdg_cdiv(width, kTile) * sdg_cdiv(height, kTile)) * 2 * sizeof(float));
-  L.maps = take(want_grad ? (size_t)views * 9 * (size_t)width * (size_t)height * sizeof(float) : 0);
-  L.total = o;
+  Layout L = {};
+  L.part = L.take((size_t)views * (size_t)(sdg_cdiv(width, kTile) * sdg_cdiv(height, kTile)) * 2 * sizeof(float));
+  L.maps = L.take(want_grad ? (size_t)views * 9 * (size_t)width * (size_t)height * sizeof(float) : 0);
   return L;
 }
 

@@ -18,8 +18,8 @@
 // pixel blends its Gaussians in one fixed order: the same input gives the same bytes.
 #include <cstring>
 
-#include "common.h"
 #include "device_math.h"
+#include "render_pass.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -278,13 +278,13 @@ __global__ __launch_bounds__(256) void k_raster_blend(BlendArgs B) {
   }
 }
 
-struct Layout {
-  size_t co, uv, rgb, depth, rect, cnt, offs, ranges, keys0, keys1, vals0, vals1, scan_tmp, sort_tmp, total;
+struct Layout : SdgBump {
+  size_t co, uv, rgb, depth, rect, cnt, offs, ranges, keys0, keys1, vals0, vals1, scan_tmp, sort_tmp;
   size_t scan_tmp_bytes, sort_tmp_bytes;
 };
 
 bool sizes_ok(int64_t n, int views, int width, int height, int64_t max_instances) {
-  if (n < 0 || n >= ((int64_t)1 << 31) || views < 0 || views > 65535) return false;
+  if (n < 0 || n >= ((int64_t)1 << 31) || views < 0 || views > rp::kMaxViews) return false;
   if (width < 1 || height < 1 || width > kMaxSide || height > kMaxSide) return false;
   if (max_instances < 1 || max_instances >= ((int64_t)1 << 31)) return false;
   const int64_t tiles = (int64_t)views * sdg_cdiv(width, kTile) * sdg_cdiv(height, kTile);
@@ -294,29 +294,25 @@ bool sizes_ok(int64_t n, int views, int width, int height, int64_t max_instances
 Layout layout(int64_t n, int views, int width, int height, int64_t max_instances) {
   const size_t vn = (size_t)views * (size_t)n, m = (size_t)max_instances;
   const size_t tiles = (size_t)views * sdg_cdiv(width, kTile) * sdg_cdiv(height, kTile);
-  Layout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += sdg_align(bytes); return at; };
-  L.co = take(vn * sizeof(float4));
-  L.uv = take(vn * sizeof(float2));
-  L.rgb = take(vn * 3 * sizeof(float));
-  L.depth = take(vn * sizeof(uint32_t));
-  L.rect = take(vn * sizeof(ushort4));
-  L.cnt = take((vn + 1) * sizeof(int64_t));
-  L.offs = take((vn + 1) * sizeof(int64_t));
-  L.ranges = take((tiles + 1) * sizeof(int2));
-  L.keys0 = take(m * sizeof(u64));
-  L.keys1 = take(m * sizeof(u64));
-  L.vals0 = take(m * sizeof(uint32_t));
-  L.vals1 = take(m * sizeof(uint32_t));
+  Layout L = {};
+  L.co = L.take(vn * sizeof(float4));
+  L.uv = L.take(vn * sizeof(float2));
+  L.rgb = L.take(vn * 3 * sizeof(float));
+  L.depth = L.take(vn * sizeof(uint32_t));
+  L.rect = L.take(vn * sizeof(ushort4));
+  L.cnt = L.take((vn + 1) * sizeof(int64_t));
+  L.offs = L.take((vn + 1) * sizeof(int64_t));
+  L.ranges = L.take((tiles + 1) * sizeof(int2));
+  L.keys0 = L.take(m * sizeof(u64));
+  L.keys1 = L.take(m * sizeof(u64));
+  L.vals0 = L.take(m * sizeof(uint32_t));
+  L.vals1 = L.take(m * sizeof(uint32_t));
   L.scan_tmp_bytes = scan_tmp_bound(vn + 1);
   L.sort_tmp_bytes = sort_tmp_bound(m);
-  L.scan_tmp = take(L.scan_tmp_bytes);
-  L.sort_tmp = take(L.sort_tmp_bytes);
-  L.total = o;
+  L.scan_tmp = L.take(L.scan_tmp_bytes);
+  L.sort_tmp = L.take(L.sort_tmp_bytes);
   return L;
 }
-
 
 // ---- backward (include/sixdgs.h, sixdgs_raster_views_backward) ---------------------------------------------------------------------
 //   blend_bwd    k_raster_blend_bwd    one workgroup per tile, one pixel per lane.  Phase A repeats the forward walk (final T, where
@@ -814,17 +810,14 @@ __global__ __launch_bounds__(256) void k_raster_cams_bwd(const int64_t* __restri
   if (tid < 16) d_cams[view * 16 + tid] = acc;
 }
 
-struct BwdLayout {
-  size_t slots, cam_part, total;
+struct BwdLayout : SdgBump {
+  size_t slots, cam_part;
 };
 
 BwdLayout bwd_layout(int64_t n, int views, int64_t max_instances) {
-  BwdLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += sdg_align(bytes); return at; };
-  L.slots = take((size_t)max_instances * kSlot * sizeof(float));
-  L.cam_part = take((size_t)views * (size_t)sdg_cdiv(n, 256) * 16 * sizeof(float));
-  L.total = o;
+  BwdLayout L = {};
+  L.slots = L.take((size_t)max_instances * kSlot * sizeof(float));
+  L.cam_part = L.take((size_t)views * (size_t)sdg_cdiv(n, 256) * 16 * sizeof(float));
   return L;
 }
 
@@ -843,12 +836,11 @@ int sixdgs_raster_views(const float* xyz, const float* scale, int scale_is_log, 
                         float* image_f32, uint8_t* image_u8, int channels, int32_t* radii, int64_t max_instances, int64_t* instances,
                         void* ws, size_t ws_bytes, sixdgs_stream_t stream, sixdgs_profile* prof) {
   SDG_CHECK_ARG(sizes_ok(n, views, width, height, max_instances));
+  const rp::Scene S = {xyz, scale, rot, opacity, f_dc, f_rest, background, scale_is_log, opacity_is_logit, n_coef, n, scale_modifier};
   SDG_CHECK_ARG(channels == 3 || channels == 4);
-  SDG_CHECK_ARG(scale_modifier > 0.f && scale_modifier < INFINITY);
-  SDG_CHECK_ARG(sh_degree >= 0 && sh_degree <= 3 && n_coef >= (sh_degree + 1) * (sh_degree + 1) && n_coef <= 16);
+  SDG_CHECK_ARG(rp::scene_ok(S, sh_degree));
   if (views == 0) return 0;
-  SDG_CHECK_ARG(cams && background);
-  SDG_CHECK_ARG(n == 0 || (xyz && scale && rot && opacity && f_dc && (n_coef == 1 || f_rest)));
+  SDG_CHECK_ARG(cams && rp::scene_present(S));
   const Layout L = layout(n, views, width, height, max_instances);
   if (ws_bytes < L.total) return SIXDGS_E_WORKSPACE;
   SDG_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0);
@@ -941,12 +933,11 @@ int sixdgs_raster_views_backward(const float* xyz, const float* scale, int scale
                                  const float* grad_image, int64_t max_instances, const void* fwd_ws, size_t fwd_ws_bytes, float* d_xyz,
                                  float* d_scale, float* d_rot, float* d_opacity, float* d_f_dc, float* d_f_rest, float* d_cams, void* ws,
                                  size_t ws_bytes, sixdgs_stream_t stream, sixdgs_profile* prof) {
+  const rp::Scene S = {xyz, scale, rot, opacity, f_dc, f_rest, background, scale_is_log, opacity_is_logit, n_coef, n, scale_modifier};
   SDG_CHECK_ARG(sizes_ok(n, views, width, height, max_instances));
-  SDG_CHECK_ARG(scale_modifier > 0.f && scale_modifier < INFINITY);
-  SDG_CHECK_ARG(sh_degree >= 0 && sh_degree <= 3 && n_coef >= (sh_degree + 1) * (sh_degree + 1) && n_coef <= 16);
+  SDG_CHECK_ARG(rp::scene_ok(S, sh_degree));
   if (views == 0) return 0;
-  SDG_CHECK_ARG(cams && background && grad_image && fwd_ws);
-  SDG_CHECK_ARG(n == 0 || (xyz && scale && rot && opacity && f_dc && (n_coef == 1 || f_rest)));
+  SDG_CHECK_ARG(cams && rp::scene_present(S) && grad_image && fwd_ws);
   const Layout F = layout(n, views, width, height, max_instances);
   const BwdLayout L = bwd_layout(n, views, max_instances);
   if (fwd_ws_bytes < F.total || ws_bytes < L.total) return SIXDGS_E_WORKSPACE;

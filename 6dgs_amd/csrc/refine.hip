@@ -4,15 +4,15 @@
 // points and never reads anything back.
 #include <math.h>
 
-#include "common.h"
 #include "pose_step.h"
+#include "render_pass.h"
 
 namespace {
 
 using namespace sdg;
+using namespace rp;
 
 constexpr int kBlock = 64;
-constexpr int kMaxViews = 65535;
 
 struct StepArgs {
   const float* start;
@@ -61,11 +61,7 @@ __global__ __launch_bounds__(kBlock) void k_pose_step(StepArgs A) {
                 A.delta + d, A.m + d, A.v + d, A.rows + r, A.best_loss + v, A.best_step + v, A.best_rows + r, A.history + v, A.status + v);
 }
 
-bool adam_ok(float lr, float beta1, float beta2, float eps) {
-  return lr > 0.f && lr < INFINITY && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && eps < INFINITY;
-}
-
-bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+bool adam_ok(float lr, float beta1, float beta2, float eps) { return lr > 0.f && lr < INFINITY && hyper_ok(beta1, beta2, eps); }
 
 int launch_step(const StepArgs& A, hipStream_t s) {
   hipLaunchKernelGGL(k_pose_step, dim3((unsigned)sdg_cdiv(A.views, kBlock)), dim3(kBlock), 0, s, A);
@@ -73,35 +69,16 @@ int launch_step(const StepArgs& A, hipStream_t s) {
   return 0;
 }
 
-struct Layout {
-  size_t fwd, bwd, photo, image, grad, rows, d_rows, loss, delta, m, v, count, total;
-  size_t fwd_bytes, bwd_bytes, photo_bytes;
+struct Layout : PassLayout {
+  size_t d_rows, delta, m, v;
 };
 
-// 0 total = outside the limits (the rasteriser's: its workspace is never 0 inside them)
+// 0 total = outside the limits
 Layout layout(int64_t n, int views, int width, int height, int64_t max_instances) {
   Layout L = {};
-  L.fwd_bytes = sixdgs_raster_views_workspace_bytes(n, views, width, height, max_instances);
-  L.bwd_bytes = sixdgs_raster_views_backward_workspace_bytes(n, views, width, height, max_instances);
-  if (L.fwd_bytes == 0 || L.bwd_bytes == 0) return L;
-  L.photo_bytes = sixdgs_photometric_loss_workspace_bytes(views, width, height, 1);
-  if (views > 0 && L.photo_bytes == 0) return L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += sdg_align(bytes); return at; };
-  const size_t px = (size_t)views * (size_t)height * (size_t)width, nv = (size_t)views;
-  L.fwd = take(L.fwd_bytes);
-  L.bwd = take(L.bwd_bytes);
-  L.photo = take(L.photo_bytes);
-  L.image = take(px * 4 * sizeof(float));
-  L.grad = take(px * 4 * sizeof(float));
-  L.rows = take(nv * 16 * sizeof(float));
-  L.d_rows = take(nv * 16 * sizeof(float));
-  L.loss = take(nv * sizeof(float));
-  L.delta = take(nv * 6 * sizeof(float));
-  L.m = take(nv * 6 * sizeof(float));
-  L.v = take(nv * 6 * sizeof(float));
-  L.count = take(sizeof(int64_t));
-  L.total = o;
+  if (!pass_layout(L, n, views, width, height, max_instances)) return L;
+  L.d_rows = L.take((size_t)views * 16 * sizeof(float));
+  for (size_t* at : {&L.delta, &L.m, &L.v}) *at = L.take((size_t)views * 6 * sizeof(float));      // the motion and Adam's moments
   return L;
 }
 
@@ -151,26 +128,20 @@ int sixdgs_refine_poses(const float* xyz, const float* scale, int scale_is_log, 
                         float* best_rows, float* best_loss, int32_t* best_step, float* history, float* delta, int32_t* status,
                         int64_t* instances_needed, void* ws, size_t ws_bytes, sixdgs_stream_t stream) {
   const Layout L = layout(n, views, width, height, max_instances);
+  const Scene S = {xyz, scale, rot, opacity, f_dc, f_rest, background, scale_is_log, opacity_is_logit, n_coef, n, scale_modifier};
+  const Target T = {target, target_is_u8, target_stride};
   SDG_CHECK_ARG(L.total != 0);
-  SDG_CHECK_ARG(scale_modifier > 0.f && scale_modifier < INFINITY);
-  SDG_CHECK_ARG(sh_degree >= 0 && sh_degree <= 3 && n_coef >= (sh_degree + 1) * (sh_degree + 1) && n_coef <= 16);
-  SDG_CHECK_ARG(target_is_u8 == 0 || target_is_u8 == 1);
-  SDG_CHECK_ARG(target_is_u8 ? target_stride == 3 : (target_stride == 3 || target_stride == 4));
-  SDG_CHECK_ARG(lambda >= 0.f && lambda <= 1.f);
-  SDG_CHECK_ARG(steps >= 1 && steps < INT32_MAX - 1);
-  SDG_CHECK_ARG(adam_ok(lr, beta1, beta2, eps));
+  SDG_CHECK_ARG(scene_ok(S, sh_degree) && target_ok(T));
+  SDG_CHECK_ARG(loop_ok(lambda, steps) && adam_ok(lr, beta1, beta2, eps));
   if (views == 0) return 0;
-  SDG_CHECK_ARG(start_rows && background && target);
-  SDG_CHECK_ARG(n == 0 || (xyz && scale && rot && opacity && f_dc && (n_coef == 1 || f_rest)));
+  SDG_CHECK_ARG(start_rows && scene_present(S) && target_present(T));
   SDG_CHECK_ARG(best_rows && best_loss && best_step && history && status && instances_needed);
-  SDG_CHECK_ARG(aligned4(start_rows) && (target_is_u8 || aligned4(target)) && aligned4(best_rows) && aligned4(best_loss) && aligned4(best_step) &&
+  SDG_CHECK_ARG(aligned4(start_rows) && aligned4(best_rows) && aligned4(best_loss) && aligned4(best_step) &&
                 aligned4(history) && aligned4(delta) && aligned4(status) && ((uintptr_t)instances_needed & 7) == 0);
   if (ws_bytes < L.total) return SIXDGS_E_WORKSPACE;
   SDG_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0);
   hipStream_t s = sdg_stream(stream);
   char* w = (char*)ws;
-  float* image = (float*)(w + L.image);
-  float* grad = (float*)(w + L.grad);
   float* rows = (float*)(w + L.rows);
   float* d_rows = (float*)(w + L.d_rows);
   float* loss = (float*)(w + L.loss);
@@ -182,20 +153,10 @@ int sixdgs_refine_poses(const float* xyz, const float* scale, int scale_is_log, 
                      best_step, best_rows, status, instances_needed);
   SDG_LAUNCH_OK();
   for (int step = 0; step <= steps; ++step) {
-    const int last = step == steps;
-    int st = sixdgs_raster_views(xyz, scale, scale_is_log, rot, opacity, opacity_is_logit, f_dc, f_rest, sh_degree, n_coef, n, rows, views,
-                                 width, height, scale_modifier, background, image, nullptr, 3, nullptr, max_instances, count, w + L.fwd,
-                                 L.fwd_bytes, stream, nullptr);
+    const int last = step == steps;      // the last evaluation takes no gradient; the others the camera rows' alone
+    int st = render_pass(S, sh_degree, rows, views, width, height, T, lambda, max_instances, L, w, last ? nullptr : (float*)(w + L.grad),
+                             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, last ? nullptr : d_rows, stream);
     if (st != 0) return st;
-    st = sixdgs_photometric_loss(image, 4, target, target_is_u8, target_stride, views, width, height, lambda, nullptr, loss, nullptr,
-                                 last ? nullptr : grad, w + L.photo, L.photo_bytes, stream, nullptr);
-    if (st != 0) return st;
-    if (!last) {
-      st = sixdgs_raster_views_backward(xyz, scale, scale_is_log, rot, opacity, opacity_is_logit, f_dc, f_rest, sh_degree, n_coef, n, rows,
-                                        views, width, height, scale_modifier, background, grad, max_instances, w + L.fwd, L.fwd_bytes, nullptr,
-                                        nullptr, nullptr, nullptr, nullptr, nullptr, d_rows, w + L.bwd, L.bwd_bytes, stream, nullptr);
-      if (st != 0) return st;
-    }
     const StepArgs A = {start_rows, loss,  last ? nullptr : d_rows, count, max_instances, views, step, last, ps::adam_at(step, lr, beta1, beta2, eps),
                         dl,         m,     v,    rows,  best_loss, best_step, best_rows, history + (size_t)step * views, status,
                         instances_needed};

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import autograd, ops
-from .refine import ALPHA_MODES, BACKENDS, _stack_images, prepare_target, scaled_intrinsics
+from .refine import ALPHA_MODES, BACKENDS, check_poses, posed_views
 from .scene import GaussianScene
 
 GROUPS = ops.FIT_GROUPS
@@ -128,20 +128,8 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
         sh_degree_start = _int_at_least(sh_degree_start, 0, "sh_degree_start")
         if sh_degree_start > max_degree:
             raise ValueError(f"sh_degree_start must be at most the scene's degree {max_degree} (got {sh_degree_start})")
-    c2w = torch.as_tensor(np.asarray(c2w) if not torch.is_tensor(c2w) else c2w).detach().float()
-    if c2w.dim() != 3 or tuple(c2w.shape[1:]) != (4, 4) or c2w.shape[0] < 1:
-        raise ValueError(f"c2w must be [V,4,4] (got {tuple(c2w.shape)})")
+    c2w, K = check_poses(images, c2w, intrinsics, min_views=1)
     n_views = c2w.shape[0]
-    K = torch.as_tensor(np.asarray(intrinsics) if not torch.is_tensor(intrinsics) else intrinsics).detach().float()
-    if tuple(K.shape) == (3, 3):
-        K = K[None].expand(n_views, 3, 3)
-    if tuple(K.shape) != (n_views, 3, 3):
-        raise ValueError(f"intrinsics must be [3,3] or [{n_views},3,3] (got {tuple(K.shape)})")
-    n_images = images.shape[0] if torch.is_tensor(images) else len(images)
-    if n_images != n_views:
-        raise ValueError(f"{n_images} images for {n_views} poses")
-    if not torch.isfinite(c2w).all():
-        raise ValueError("c2w must be finite")
     if schedule is None:
         views = default_schedule(n_views, steps, batch, seed)
     else:
@@ -153,10 +141,7 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
         raise RuntimeError("6dgs_amd: fit_scene needs the scene on the GPU (no CPU fallback on the product path)")
     dev = scene._xyz.device
     params = {k: getattr(scene, a).detach().float().contiguous().clone() for k, a in _SCENE_ATTR.items()}
-    target, ox, oy = prepare_target(_stack_images(images, dev), downscale, alpha, background)
-    height, width = int(target.shape[1]), int(target.shape[2])
-    # (the 4 x 4 inversions run on the host, as refine_poses' do)
-    cams = torch.cat([torch.linalg.inv(c2w.cpu())[:, :3, :].reshape(n_views, 12), scaled_intrinsics(K.cpu(), downscale, ox, oy)], dim=1).to(dev).contiguous()
+    target, cams, width, height = posed_views(images, c2w, K, dev, downscale, alpha, background)
     # the per-step schedule, the same numbers for both backends
     lrs = np.empty((steps, len(GROUPS)), np.float64)
     for s in range(steps):

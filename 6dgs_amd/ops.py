@@ -287,6 +287,98 @@ def eval_sh_color(sh: torch.Tensor, dirs: torch.Tensor, sh_degree: int) -> torch
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# rendering a scene and comparing it with a target: what the functions below share.  Every check here runs before _need_gpu.
+# ---------------------------------------------------------------------------------------------
+RASTER_INSTANCES_PER_GAUSSIAN = 8       # first guess of the tile instances a (view, Gaussian) pair needs; an overflow is retried exactly
+RASTER_MAX_INSTANCES = (1 << 31) - 1
+SCENE_ARRAYS = ("xyz", "scale", "rot", "opacity", "f_dc", "f_rest")      # the order the rasteriser's entry points take a scene in
+
+
+def raster_instances_estimate(n: int, views: int) -> int:
+    return int(min(max(RASTER_INSTANCES_PER_GAUSSIAN * int(n) * int(views), 4096), RASTER_MAX_INSTANCES))
+
+
+def _scene_shape(xyz, scale, rot, opacity, f_dc, f_rest):
+    """(n, n_coef) of a scene's arrays, which must agree about n; rot and opacity may be None (the splatter takes neither)."""
+    n = xyz.shape[0]
+    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
+    if (xyz.shape != (n, 3) or scale.shape != (n, 3) or (rot is not None and rot.shape != (n, 4))
+            or (opacity is not None and opacity.numel() != n) or f_dc.numel() != 3 * n or f_rest.numel() != 3 * n * (n_coef - 1)):
+        raise ValueError("scene arrays disagree about the number of Gaussians")
+    return n, n_coef
+
+
+def _scene(xyz, scale, rot, opacity, f_dc, f_rest):
+    """A scene's arrays as contiguous float32 -> (the six tensors, n, n_coef)."""
+    t = tuple(None if a is None else _f32(a) for a in (xyz, scale, rot, opacity, f_dc, f_rest))
+    return (t, *_scene_shape(*t))
+
+
+def _scene_args(t, n_coef, scale_is_log, opacity_is_logit):
+    """The eight arguments the rasteriser's entry points begin with."""
+    xyz, scale, rot, opacity, f_dc, f_rest = t
+    return (_p(xyz), _p(scale), int(scale_is_log), _p(rot), _p(opacity), int(opacity_is_logit), _p(f_dc), _p(f_rest if n_coef > 1 else None))
+
+
+def _view_args(cams, width, height, background, scale_modifier=1.0, name="cams"):
+    """The arguments that say how the views are drawn -> (cams as contiguous float32, width, height)."""
+    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
+        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
+    if int(width) < 1 or int(height) < 1:
+        raise ValueError(f"width and height must be positive (got {width} x {height})")
+    if not torch.is_tensor(cams) or cams.dim() != 2 or cams.shape[1] != 16:
+        raise ValueError(f"{name} must be a [views,16] tensor (got {tuple(cams.shape) if torch.is_tensor(cams) else type(cams).__name__})")
+    if len(background) != 3:
+        raise ValueError("background must have 3 entries")
+    return _f32(cams), int(width), int(height)
+
+
+def _background(background, dev):
+    return torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
+
+
+def _target_args(target, views, height, width):
+    """A target image, fp32 [views,height,width,3|4] or uint8 [views,height,width,3] and contiguous -> (target, is_u8, stride)."""
+    if not torch.is_tensor(target) or target.dim() != 4 or tuple(target.shape[:3]) != (views, height, width):
+        raise ValueError(f"target must be a [{views},{height},{width},3|4] tensor (got {tuple(target.shape) if torch.is_tensor(target) else type(target).__name__})")
+    if target.dtype == torch.uint8:
+        if target.shape[3] != 3:
+            raise ValueError("a uint8 target must have 3 channels")
+    elif target.dtype != torch.float32 or target.shape[3] not in (3, 4):
+        raise ValueError(f"target must be float32 with 3 or 4 channels, or uint8 with 3 (got {target.dtype} with {target.shape[3]})")
+    if not target.is_contiguous():
+        raise ValueError("target must be contiguous")
+    return target.detach(), int(target.dtype == torch.uint8), int(target.shape[3])
+
+
+def _lambda(lambda_dssim) -> float:
+    if not 0.0 <= float(lambda_dssim) <= 1.0:
+        raise ValueError(f"lambda_dssim must be in [0, 1] (got {lambda_dssim})")
+    return float(lambda_dssim)
+
+
+def _capacity(max_instances, n, views) -> int:
+    """The instance capacity a call starts with: the caller's, or the estimate."""
+    if max_instances is None:
+        return raster_instances_estimate(n, views)
+    if not 1 <= int(max_instances) <= RASTER_MAX_INSTANCES:
+        raise ValueError(f"max_instances must be in [1, 2^31) (got {max_instances})")
+    return int(max_instances)
+
+
+def _grown(needed: int) -> int:
+    """The capacity of the next run of a fused loop that overflowed: 5/4 of what it needed."""
+    return min(max(needed + needed // 4, 1), RASTER_MAX_INSTANCES)
+
+
+def _workspace(workspace, need, dev):
+    """The caller's workspace if it holds `need` bytes, else a new one -> (the tensor, its bytes)."""
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    return workspace, workspace.numel() * workspace.element_size()
+
+
 def splat_views_workspace_bytes(n: int, views: int, width: int, height: int) -> int:
     return int(_lib.load().sixdgs_splat_views_workspace_bytes(int(n), int(views), int(width), int(height)))
 
@@ -304,43 +396,25 @@ def splat_views(xyz, scale, f_dc, f_rest, sh_degree: int, cams: torch.Tensor, wi
         raise ValueError(f"extent must be positive and finite (got {extent})")
     if not float(near_z) >= 0.0:
         raise ValueError(f"near_z must be >= 0 (got {near_z})")
-    if int(width) < 1 or int(height) < 1:
-        raise ValueError(f"width and height must be positive (got {width} x {height})")
-    if not torch.is_tensor(cams) or cams.dim() != 2 or cams.shape[1] != 16:
-        raise ValueError(f"cams must be a [views,16] tensor (got {tuple(cams.shape) if torch.is_tensor(cams) else type(cams).__name__})")
-    if len(background) != 3:
-        raise ValueError("background must have 3 entries")
-    xyz, scale, f_dc, f_rest, cams = _f32(xyz), _f32(scale), _f32(f_dc), _f32(f_rest), _f32(cams)
-    n, views = xyz.shape[0], cams.shape[0]
-    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
-    if xyz.shape != (n, 3) or scale.shape != (n, 3) or f_dc.numel() != 3 * n or f_rest.numel() != 3 * n * (n_coef - 1):
-        raise ValueError("scene arrays disagree about the number of Gaussians")
+    cams, width, height = _view_args(cams, width, height, background)
+    (xyz, scale, _, _, f_dc, f_rest), n, n_coef = _scene(xyz, scale, None, None, f_dc, f_rest)
+    views = cams.shape[0]
     _need_gpu(xyz, scale, f_dc, f_rest, cams, workspace)
     lib = _lib.load()
     dev = xyz.device
-    need = lib.sixdgs_splat_views_workspace_bytes(n, views, int(width), int(height))
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    bg = torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
-    image = torch.empty(views, int(height), int(width), channels, dtype=torch.uint8, device=dev)
-    winner = torch.empty(views, int(height), int(width), dtype=torch.int32, device=dev) if want_winner else None
+    ws, ws_bytes = _workspace(workspace, lib.sixdgs_splat_views_workspace_bytes(n, views, width, height), dev)
+    bg = _background(background, dev)
+    image = torch.empty(views, height, width, channels, dtype=torch.uint8, device=dev)
+    winner = torch.empty(views, height, width, dtype=torch.int32, device=dev) if want_winner else None
     check(lib.sixdgs_splat_views(_p(xyz), _p(scale), int(scale_is_log), _p(f_dc), _p(f_rest if n_coef > 1 else None), int(sh_degree),
-                                 int(n_coef), n, _p(cams), views, int(width), int(height), int(channels), float(extent), float(near_z),
-                                 _p(bg), _p(image), _p(winner), _p(workspace), workspace.numel() * workspace.element_size(), _stream()),
+                                 int(n_coef), n, _p(cams), views, width, height, int(channels), float(extent), float(near_z),
+                                 _p(bg), _p(image), _p(winner), _p(ws), ws_bytes, _stream()),
           "splat_views")
     return (image, winner) if want_winner else image
 
 
-RASTER_INSTANCES_PER_GAUSSIAN = 8       # first guess of the tile instances a (view, Gaussian) pair needs; an overflow is retried exactly
-RASTER_MAX_INSTANCES = (1 << 31) - 1
-
-
 def raster_views_workspace_bytes(n: int, views: int, width: int, height: int, max_instances: int) -> int:
     return int(_lib.load().sixdgs_raster_views_workspace_bytes(int(n), int(views), int(width), int(height), int(max_instances)))
-
-
-def raster_instances_estimate(n: int, views: int) -> int:
-    return int(min(max(RASTER_INSTANCES_PER_GAUSSIAN * int(n) * int(views), 4096), RASTER_MAX_INSTANCES))
 
 
 @_on_device
@@ -358,46 +432,29 @@ def raster_views(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: t
     raster_views_backward: (the workspace tensor the call ran in, the capacity it ran with)."""
     if channels not in (3, 4):
         raise ValueError(f"channels must be 3 or 4 (got {channels})")
-    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
-        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
-    if int(width) < 1 or int(height) < 1:
-        raise ValueError(f"width and height must be positive (got {width} x {height})")
-    if not torch.is_tensor(cams) or cams.dim() != 2 or cams.shape[1] != 16:
-        raise ValueError(f"cams must be a [views,16] tensor (got {tuple(cams.shape) if torch.is_tensor(cams) else type(cams).__name__})")
-    if len(background) != 3:
-        raise ValueError("background must have 3 entries")
+    cams, width, height = _view_args(cams, width, height, background, scale_modifier)
     if not (want_float or want_u8 or want_radii or want_instances or want_state):
         raise ValueError("nothing asked for: want_float, want_u8, want_radii and want_instances are all off")
-    if max_instances is not None and not 1 <= int(max_instances) <= RASTER_MAX_INSTANCES:
-        raise ValueError(f"max_instances must be in [1, 2^31) (got {max_instances})")
-    xyz, scale, rot, opacity, f_dc, f_rest, cams = _f32(xyz), _f32(scale), _f32(rot), _f32(opacity), _f32(f_dc), _f32(f_rest), _f32(cams)
-    n, views = xyz.shape[0], cams.shape[0]
-    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
-    if (xyz.shape != (n, 3) or scale.shape != (n, 3) or rot.shape != (n, 4) or opacity.numel() != n or f_dc.numel() != 3 * n
-            or f_rest.numel() != 3 * n * (n_coef - 1)):
-        raise ValueError("scene arrays disagree about the number of Gaussians")
-    _need_gpu(xyz, scale, rot, opacity, f_dc, f_rest, cams, workspace)
+    scene, n, n_coef = _scene(xyz, scale, rot, opacity, f_dc, f_rest)
+    views = cams.shape[0]
+    capacity = _capacity(max_instances, n, views)
+    _need_gpu(*scene, cams, workspace)
     lib = _lib.load()
-    dev = xyz.device
-    width, height = int(width), int(height)
-    bg = torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
+    dev = scene[0].device
+    bg = _background(background, dev)
     image_f = torch.empty(views, height, width, 4, dtype=torch.float32, device=dev) if want_float else None
     image_u = torch.empty(views, height, width, channels, dtype=torch.uint8, device=dev) if want_u8 else None
     radii = torch.empty(views, n, dtype=torch.int32, device=dev) if want_radii else None
     count = torch.zeros(1, dtype=torch.int64, device=dev)
-    capacity = int(max_instances) if max_instances is not None else raster_instances_estimate(n, views)
     needed = 0
     for attempt in range(2):
         need = lib.sixdgs_raster_views_workspace_bytes(n, views, width, height, capacity)
         if need == 0 and views > 0:
             raise ValueError(f"sizes outside the rasteriser's limits (n {n}, views {views}, {width} x {height}, instances {capacity})")
-        ws = workspace
-        if ws is None or ws.numel() * ws.element_size() < need:
-            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        check(lib.sixdgs_raster_views(_p(xyz), _p(scale), int(scale_is_log), _p(rot), _p(opacity), int(opacity_is_logit), _p(f_dc),
-                                      _p(f_rest if n_coef > 1 else None), int(sh_degree), int(n_coef), n, _p(cams), views, width, height,
-                                      float(scale_modifier), _p(bg), _p(image_f), _p(image_u), int(channels), _p(radii), capacity,
-                                      _p(count), _p(ws), ws.numel() * ws.element_size(), _stream(), profile),
+        ws, ws_bytes = _workspace(workspace, need, dev)
+        check(lib.sixdgs_raster_views(*_scene_args(scene, n_coef, scale_is_log, opacity_is_logit), int(sh_degree), int(n_coef), n, _p(cams),
+                                      views, width, height, float(scale_modifier), _p(bg), _p(image_f), _p(image_u), int(channels), _p(radii),
+                                      capacity, _p(count), _p(ws), ws_bytes, _stream(), profile),
               "raster_views")
         needed = int(count.item()) if views > 0 else 0
         if needed <= capacity:
@@ -414,7 +471,7 @@ def raster_views_backward_workspace_bytes(n: int, views: int, width: int, height
     return int(_lib.load().sixdgs_raster_views_backward_workspace_bytes(int(n), int(views), int(width), int(height), int(max_instances)))
 
 
-RASTER_GRADIENTS = ("xyz", "scale", "rot", "opacity", "f_dc", "f_rest", "cams")
+RASTER_GRADIENTS = SCENE_ARRAYS + ("cams",)
 
 
 @_on_device
@@ -426,14 +483,7 @@ def raster_views_backward(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int
     [V,height,width,4] = dL / d image_f32; state = (workspace, capacity) of a raster_views(..., want_state=True) call on the same
     arguments, not written since.  Returns a tuple in the order of RASTER_GRADIENTS -- d xyz [N,3], d scale [N,3], d rot [N,4],
     d opacity (the shape of opacity), d f_dc, d f_rest (their shapes), d cams [V,16] -- with None for the names not in `want`."""
-    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
-        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
-    if int(width) < 1 or int(height) < 1:
-        raise ValueError(f"width and height must be positive (got {width} x {height})")
-    if not torch.is_tensor(cams) or cams.dim() != 2 or cams.shape[1] != 16:
-        raise ValueError(f"cams must be a [views,16] tensor (got {tuple(cams.shape) if torch.is_tensor(cams) else type(cams).__name__})")
-    if len(background) != 3:
-        raise ValueError("background must have 3 entries")
+    cams, width, height = _view_args(cams, width, height, background, scale_modifier)
     want = tuple(want)
     if not want or any(w not in RASTER_GRADIENTS for w in want):
         raise ValueError(f"want must name some of {RASTER_GRADIENTS} (got {want})")
@@ -441,34 +491,26 @@ def raster_views_backward(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int
             or not 1 <= int(state[1]) <= RASTER_MAX_INSTANCES):
         raise ValueError("state must be the (workspace, capacity) pair of raster_views(..., want_state=True)")
     fwd_ws, capacity = state[0], int(state[1])
-    xyz, scale, rot, opacity, f_dc, f_rest, cams = _f32(xyz), _f32(scale), _f32(rot), _f32(opacity), _f32(f_dc), _f32(f_rest), _f32(cams)
-    n, views = xyz.shape[0], cams.shape[0]
-    width, height = int(width), int(height)
-    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
-    if (xyz.shape != (n, 3) or scale.shape != (n, 3) or rot.shape != (n, 4) or opacity.numel() != n or f_dc.numel() != 3 * n
-            or f_rest.numel() != 3 * n * (n_coef - 1)):
-        raise ValueError("scene arrays disagree about the number of Gaussians")
+    scene, n, n_coef = _scene(xyz, scale, rot, opacity, f_dc, f_rest)
+    views = cams.shape[0]
     if not torch.is_tensor(grad_image) or tuple(grad_image.shape) != (views, height, width, 4):
         raise ValueError(f"grad_image must be a [{views},{height},{width},4] tensor")
     grad_image = _f32(grad_image)
-    _need_gpu(xyz, scale, rot, opacity, f_dc, f_rest, cams, grad_image, fwd_ws, workspace)
+    _need_gpu(*scene, cams, grad_image, fwd_ws, workspace)
     lib = _lib.load()
-    dev = xyz.device
+    dev = scene[0].device
     need = lib.sixdgs_raster_views_backward_workspace_bytes(n, views, width, height, capacity)
     if need == 0 and views > 0:
         raise ValueError(f"sizes outside the rasteriser's limits (n {n}, views {views}, {width} x {height}, instances {capacity})")
-    ws = workspace
-    if ws is None or ws.numel() * ws.element_size() < need:
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    bg = torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
-    like = {"xyz": xyz, "scale": scale, "rot": rot, "opacity": opacity, "f_dc": f_dc, "f_rest": f_rest, "cams": cams}
+    ws, ws_bytes = _workspace(workspace, need, dev)
+    bg = _background(background, dev)
+    like = dict(zip(RASTER_GRADIENTS, (*scene, cams)))
     # (views == 0 launches nothing: zeros are the sum over no views)
     out = {k: (torch.zeros_like(like[k]) if views == 0 else torch.empty_like(like[k])) for k in want}
-    check(lib.sixdgs_raster_views_backward(_p(xyz), _p(scale), int(scale_is_log), _p(rot), _p(opacity), int(opacity_is_logit), _p(f_dc),
-                                           _p(f_rest if n_coef > 1 else None), int(sh_degree), int(n_coef), n, _p(cams), views, width,
-                                           height, float(scale_modifier), _p(bg), _p(grad_image), capacity, _p(fwd_ws),
-                                           fwd_ws.numel() * fwd_ws.element_size(), *[_p(out.get(k)) for k in RASTER_GRADIENTS],
-                                           _p(ws), ws.numel() * ws.element_size(), _stream(), profile),
+    check(lib.sixdgs_raster_views_backward(*_scene_args(scene, n_coef, scale_is_log, opacity_is_logit), int(sh_degree), int(n_coef), n,
+                                           _p(cams), views, width, height, float(scale_modifier), _p(bg), _p(grad_image), capacity,
+                                           _p(fwd_ws), fwd_ws.numel() * fwd_ws.element_size(), *[_p(out.get(k)) for k in RASTER_GRADIENTS],
+                                           _p(ws), ws_bytes, _stream(), profile),
           "raster_views_backward")
     return tuple(out.get(k) for k in RASTER_GRADIENTS)
 
@@ -485,49 +527,36 @@ def photometric_loss(image: torch.Tensor, target: torch.Tensor, *, lambda_dssim:
     image fp32 [V,H,W,3|4] (4: raster_views' float image; its fourth channel is not read); target fp32 [V,H,W,3|4] or uint8 [V,H,W,3]
     (value u / 255); both contiguous and on one GPU.  Returns loss [V], then -- as far as asked for -- grad_image, the image's shape,
     = grad_loss[v] d loss_v / d image (grad_loss [V], None: ones; want_grad), and parts [V,2] = (l1, ssim) (want_parts)."""
-    lam = float(lambda_dssim)
-    if not 0.0 <= lam <= 1.0:
-        raise ValueError(f"lambda_dssim must be in [0, 1] (got {lambda_dssim})")
+    lam = _lambda(lambda_dssim)
     if not torch.is_tensor(image) or image.dim() != 4 or image.shape[3] not in (3, 4):
         raise ValueError(f"image must be a [views,height,width,3|4] tensor (got {tuple(image.shape) if torch.is_tensor(image) else type(image).__name__})")
     if image.dtype != torch.float32:
         raise ValueError(f"image must be float32 (got {image.dtype})")
+    if not image.is_contiguous():
+        raise ValueError("image must be contiguous")
     views, height, width, stride = image.shape
-    if not torch.is_tensor(target) or target.dim() != 4 or tuple(target.shape[:3]) != (views, height, width):
-        raise ValueError(f"target must be a [{views},{height},{width},3|4] tensor (got {tuple(target.shape) if torch.is_tensor(target) else type(target).__name__})")
-    if target.dtype == torch.uint8:
-        if target.shape[3] != 3:
-            raise ValueError("a uint8 target must have 3 channels")
-    elif target.dtype != torch.float32:
-        raise ValueError(f"target must be float32 or uint8 (got {target.dtype})")
-    elif target.shape[3] not in (3, 4):
-        raise ValueError("target must have 3 or 4 channels")
     if width < 1 or height < 1:
         raise ValueError(f"width and height must be positive (got {width} x {height})")
-    if not image.is_contiguous() or not target.is_contiguous():
-        raise ValueError("image and target must be contiguous")
+    target, target_is_u8, target_stride = _target_args(target, views, height, width)
     if grad_loss is not None:
         if not want_grad:
             raise ValueError("grad_loss without want_grad")
         if not torch.is_tensor(grad_loss) or tuple(grad_loss.shape) != (views,):
             raise ValueError(f"grad_loss must be a [{views}] tensor")
         grad_loss = _f32(grad_loss)
-    image, target = image.detach(), target.detach()
+    image = image.detach()
     _need_gpu(image, target, grad_loss, workspace)
     lib = _lib.load()
     dev = image.device
     need = lib.sixdgs_photometric_loss_workspace_bytes(views, width, height, int(want_grad))
     if need == 0 and views > 0:
         raise ValueError(f"sizes outside the photometric loss's limits (views {views}, {width} x {height})")
-    ws = workspace
-    if ws is None or ws.numel() * ws.element_size() < need:
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace(workspace, need, dev)
     loss = torch.empty(views, dtype=torch.float32, device=dev)
     parts = torch.empty(views, 2, dtype=torch.float32, device=dev) if want_parts else None
     grad = torch.empty_like(image) if want_grad else None
-    check(lib.sixdgs_photometric_loss(_p(image), stride, _p(target), int(target.dtype == torch.uint8), int(target.shape[3]), views, width,
-                                      height, lam, _p(grad_loss), _p(loss), _p(parts), _p(grad), _p(ws), ws.numel() * ws.element_size(),
-                                      _stream(), profile),
+    check(lib.sixdgs_photometric_loss(_p(image), stride, _p(target), target_is_u8, target_stride, views, width, height, lam, _p(grad_loss),
+                                      _p(loss), _p(parts), _p(grad), _p(ws), ws_bytes, _stream(), profile),
           "photometric_loss")
     out = [loss] + [o for o, want in ((grad, want_grad), (parts, want_parts)) if want]
     return out[0] if len(out) == 1 else tuple(out)
@@ -639,60 +668,34 @@ def refine_poses_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, sta
     instances_needed (int) and max_instances (int: the capacity of the run returned).  The call runs with raster_instances_estimate's capacity (or max_instances), reads status and
     instances_needed once at the end, and -- with retry -- on bit 1 runs again from the start with 5/4 of the needed capacity, at most
     REFINE_ATTEMPTS runs in all, then RuntimeError."""
-    lam = float(lambda_dssim)
-    if not 0.0 <= lam <= 1.0:
-        raise ValueError(f"lambda_dssim must be in [0, 1] (got {lambda_dssim})")
+    lam = _lambda(lambda_dssim)
     if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
         raise ValueError(f"steps must be a positive integer (got {steps})")
     _check_adam(lr, beta1, beta2, eps)
-    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
-        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
-    if int(width) < 1 or int(height) < 1:
-        raise ValueError(f"width and height must be positive (got {width} x {height})")
-    if len(background) != 3:
-        raise ValueError("background must have 3 entries")
-    if max_instances is not None and not 1 <= int(max_instances) <= RASTER_MAX_INSTANCES:
-        raise ValueError(f"max_instances must be in [1, 2^31) (got {max_instances})")
-    if not torch.is_tensor(start_rows) or start_rows.dim() != 2 or start_rows.shape[1] != 16:
-        raise ValueError("start_rows must be a [views,16] tensor")
-    xyz, scale, rot, opacity, f_dc, f_rest, start_rows = (_f32(xyz), _f32(scale), _f32(rot), _f32(opacity), _f32(f_dc), _f32(f_rest),
-                                                          _f32(start_rows))
-    n, views, steps, width, height = xyz.shape[0], start_rows.shape[0], int(steps), int(width), int(height)
-    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
-    if (xyz.shape != (n, 3) or scale.shape != (n, 3) or rot.shape != (n, 4) or opacity.numel() != n or f_dc.numel() != 3 * n
-            or f_rest.numel() != 3 * n * (n_coef - 1)):
-        raise ValueError("scene arrays disagree about the number of Gaussians")
-    if not torch.is_tensor(target) or target.dim() != 4 or tuple(target.shape[:3]) != (views, height, width):
-        raise ValueError(f"target must be a [{views},{height},{width},3|4] tensor")
-    if target.dtype == torch.uint8:
-        if target.shape[3] != 3:
-            raise ValueError("a uint8 target must have 3 channels")
-    elif target.dtype != torch.float32 or target.shape[3] not in (3, 4):
-        raise ValueError("target must be float32 with 3 or 4 channels, or uint8 with 3")
-    if not target.is_contiguous():
-        raise ValueError("target must be contiguous")
-    target = target.detach()
-    _need_gpu(xyz, scale, rot, opacity, f_dc, f_rest, start_rows, target)
+    start_rows, width, height = _view_args(start_rows, width, height, background, scale_modifier, "start_rows")
+    scene, n, n_coef = _scene(xyz, scale, rot, opacity, f_dc, f_rest)
+    views, steps = start_rows.shape[0], int(steps)
+    capacity = _capacity(max_instances, n, views)
+    target, target_is_u8, target_stride = _target_args(target, views, height, width)
+    _need_gpu(*scene, start_rows, target)
     lib = _lib.load()
-    dev = xyz.device
-    bg = torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
+    dev = scene[0].device
+    bg = _background(background, dev)
     out = {"best_rows": torch.empty(views, 16, device=dev), "best_loss": torch.empty(views, device=dev),
            "best_step": torch.empty(views, dtype=torch.int32, device=dev), "history": torch.empty(steps + 1, views, device=dev),
            "delta": torch.empty(views, 6, device=dev), "status": torch.empty(views, dtype=torch.int32, device=dev)}
     needed_t = torch.zeros(1, dtype=torch.int64, device=dev)
-    capacity = int(max_instances) if max_instances is not None else raster_instances_estimate(n, views)
     needed = 0
     for attempt in range(REFINE_ATTEMPTS):
         need = lib.sixdgs_refine_poses_workspace_bytes(n, views, width, height, capacity)
         if need == 0:
             raise ValueError(f"sizes outside the rasteriser's limits (n {n}, views {views}, {width} x {height}, instances {capacity})")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        check(lib.sixdgs_refine_poses(_p(xyz), _p(scale), int(scale_is_log), _p(rot), _p(opacity), int(opacity_is_logit), _p(f_dc),
-                                      _p(f_rest if n_coef > 1 else None), int(sh_degree), int(n_coef), n, _p(start_rows), views, width, height,
-                                      float(scale_modifier), _p(bg), _p(target), int(target.dtype == torch.uint8), int(target.shape[3]), lam,
-                                      steps, float(lr), float(beta1), float(beta2), float(eps), capacity, _p(out["best_rows"]),
-                                      _p(out["best_loss"]), _p(out["best_step"]), _p(out["history"]), _p(out["delta"]), _p(out["status"]),
-                                      _p(needed_t), _p(ws), need, _stream()),
+        ws, ws_bytes = _workspace(None, need, dev)
+        check(lib.sixdgs_refine_poses(*_scene_args(scene, n_coef, scale_is_log, opacity_is_logit), int(sh_degree), int(n_coef), n,
+                                      _p(start_rows), views, width, height, float(scale_modifier), _p(bg), _p(target), target_is_u8,
+                                      target_stride, lam, steps, float(lr), float(beta1), float(beta2), float(eps), capacity,
+                                      _p(out["best_rows"]), _p(out["best_loss"]), _p(out["best_step"]), _p(out["history"]), _p(out["delta"]),
+                                      _p(out["status"]), _p(needed_t), _p(ws), ws_bytes, _stream()),
               "refine_poses")
         if views == 0:
             break
@@ -704,7 +707,7 @@ def refine_poses_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, sta
         if attempt == REFINE_ATTEMPTS - 1 or needed > RASTER_MAX_INSTANCES:
             raise RuntimeError(f"6dgs_amd: refine_poses still needs {needed} tile instances after {attempt + 1} runs (limit 2^31 - 1): "
                                "refine fewer views at once")
-        capacity = min(max(needed + needed // 4, 1), RASTER_MAX_INSTANCES)
+        capacity = _grown(needed)
     out["instances_needed"] = needed
     out["max_instances"] = capacity
     return out
@@ -739,12 +742,9 @@ def _fit_params(params, what="params"):
         t = params[k]
         if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError(f"{what}[{k!r}] must be a contiguous float32 tensor")
-    n = params["xyz"].shape[0]
-    f_rest = params["f_rest"]
-    n_coef = 1 + (f_rest.shape[1] if f_rest.dim() == 3 else 0)
-    if (params["xyz"].shape != (n, 3) or params["scale"].shape != (n, 3) or params["rot"].shape != (n, 4) or params["opacity"].numel() != n
-            or params["f_dc"].numel() != 3 * n or f_rest.numel() != 3 * n * (n_coef - 1) or not 1 <= n_coef <= 16):
-        raise ValueError("scene arrays disagree about the number of Gaussians")
+    n, n_coef = _scene_shape(*[params[k] for k in SCENE_ARRAYS])
+    if n_coef > 16:
+        raise ValueError(f"f_rest holds {n_coef - 1} coefficients per channel (at most 15)")
     return n, n_coef
 
 
@@ -850,27 +850,17 @@ def fit_scene_raw(params: dict, cams: torch.Tensor, width: int, height: int, tar
     runs with raster_instances_estimate's capacity (or max_instances), reads status and instances_needed once at the end, and -- with
     retry -- on bit 1 puts back the copy of the scene it took before the call and runs once more with 5/4 of the needed capacity."""
     n, n_coef = _fit_params(params)
-    lam = float(lambda_dssim)
-    if not 0.0 <= lam <= 1.0:
-        raise ValueError(f"lambda_dssim must be in [0, 1] (got {lambda_dssim})")
+    lam = _lambda(lambda_dssim)
     _check_fit_hyper(beta1, beta2, eps)
     if not (0.0 < float(reset_ceiling) < 1.0):
         raise ValueError(f"reset_ceiling must be in (0, 1) (got {reset_ceiling})")
-    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
-        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
-    if int(width) < 1 or int(height) < 1:
-        raise ValueError(f"width and height must be positive (got {width} x {height})")
-    if len(background) != 3:
-        raise ValueError("background must have 3 entries")
-    if max_instances is not None and not 1 <= int(max_instances) <= RASTER_MAX_INSTANCES:
-        raise ValueError(f"max_instances must be in [1, 2^31) (got {max_instances})")
     groups = tuple(groups)
     if not groups or any(k not in FIT_GROUPS for k in groups) or len(set(groups)) != len(groups):
         raise ValueError(f"groups must name some of {FIT_GROUPS}, each once (got {groups})")
-    if not torch.is_tensor(cams) or cams.dim() != 2 or cams.shape[1] != 16 or cams.shape[0] < 1:
+    cams, width, height = _view_args(cams, width, height, background, scale_modifier)
+    n_views = cams.shape[0]
+    if n_views < 1:
         raise ValueError("cams must be a [views,16] tensor of at least one view")
-    cams = _f32(cams)
-    n_views, width, height = cams.shape[0], int(width), int(height)
     view_t = torch.as_tensor(views).detach().cpu()
     if view_t.dim() != 2 or view_t.shape[0] < 1 or view_t.shape[1] < 1 or view_t.dtype.is_floating_point or view_t.dtype == torch.bool:
         raise ValueError("views must be an integer [steps,batch] array")
@@ -891,41 +881,30 @@ def fit_scene_raw(params: dict, cams: torch.Tensor, width: int, height: int, tar
         raise ValueError(f"resets must be [{steps}] flags")
     if bool(reset_t.any()) and not opacity_is_logit:
         raise ValueError("an opacity reset needs opacity_is_logit")
-    if not torch.is_tensor(target) or target.dim() != 4 or tuple(target.shape[:3]) != (n_views, height, width):
-        raise ValueError(f"target must be a [{n_views},{height},{width},3|4] tensor")
-    if target.dtype == torch.uint8:
-        if target.shape[3] != 3:
-            raise ValueError("a uint8 target must have 3 channels")
-    elif target.dtype != torch.float32 or target.shape[3] not in (3, 4):
-        raise ValueError("target must be float32 with 3 or 4 channels, or uint8 with 3")
-    if not target.is_contiguous():
-        raise ValueError("target must be contiguous")
-    target = target.detach()
-    arrays = [params[k] for k in FIT_GROUPS]
+    target, target_is_u8, target_stride = _target_args(target, n_views, height, width)
+    capacity = _capacity(max_instances, n, batch)
+    arrays = [params[k] for k in SCENE_ARRAYS]
     _need_gpu(*arrays, cams, target)
     lib = _lib.load()
     dev = cams.device
-    bg = torch.tensor([float(b) for b in background], dtype=torch.float32).to(dev)
+    bg = _background(background, dev)
     size = n * (11 + 3 * n_coef)
     out = {"history": torch.empty(steps, batch, device=dev), "m": torch.empty(size, device=dev), "v": torch.empty(size, device=dev),
            "status": torch.empty(1, dtype=torch.int32, device=dev)}
     needed_t = torch.zeros(1, dtype=torch.int64, device=dev)
     mask = sum(1 << FIT_GROUPS.index(k) for k in groups)
-    capacity = int(max_instances) if max_instances is not None else raster_instances_estimate(n, batch)
     saved = [t.clone() for t in arrays] if retry else None      # a run that overflowed has moved the scene up to that step
     needed = 0
     for attempt in range(2):
         need = lib.sixdgs_fit_scene_workspace_bytes(n, n_coef, batch, width, height, capacity)
         if need == 0:
             raise ValueError(f"sizes outside the rasteriser's limits (n {n}, batch {batch}, {width} x {height}, instances {capacity})")
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        p = params
-        check(lib.sixdgs_fit_scene(_p(p["xyz"]), _p(p["scale"]), int(scale_is_log), _p(p["rot"]), _p(p["opacity"]), int(opacity_is_logit),
-                                   _p(p["f_dc"]), _p(p["f_rest"] if n_coef > 1 else None), n_coef, n, _p(cams), n_views, width, height,
-                                   float(scale_modifier), _p(bg), _p(target), int(target.dtype == torch.uint8), int(target.shape[3]), lam, steps,
-                                   batch, C.c_void_p(view_t.data_ptr()), C.c_void_p(lr_t.data_ptr()), C.c_void_p(deg_t.data_ptr()),
-                                   C.c_void_p(reset_t.data_ptr()), mask, float(beta1), float(beta2), float(eps), float(reset_ceiling), capacity,
-                                   _p(out["m"]), _p(out["v"]), _p(out["history"]), _p(out["status"]), _p(needed_t), _p(ws), need, _stream()),
+        ws, ws_bytes = _workspace(None, need, dev)
+        check(lib.sixdgs_fit_scene(*_scene_args(arrays, n_coef, scale_is_log, opacity_is_logit), n_coef, n, _p(cams), n_views, width, height,
+                                   float(scale_modifier), _p(bg), _p(target), target_is_u8, target_stride, lam, steps, batch, _p(view_t),
+                                   _p(lr_t), _p(deg_t), _p(reset_t), mask, float(beta1), float(beta2), float(eps), float(reset_ceiling),
+                                   capacity, _p(out["m"]), _p(out["v"]), _p(out["history"]), _p(out["status"]), _p(needed_t), _p(ws), ws_bytes,
+                                   _stream()),
               "fit_scene")
         # the one host read of the call: the status word and the largest instance count seen
         flags = torch.cat([out["status"].to(torch.int64), needed_t]).cpu()
@@ -937,7 +916,7 @@ def fit_scene_raw(params: dict, cams: torch.Tensor, width: int, height: int, tar
                                "fit fewer views at once")
         for t, s in zip(arrays, saved):
             t.copy_(s)
-        capacity = min(max(needed + needed // 4, 1), RASTER_MAX_INSTANCES)
+        capacity = _grown(needed)
     out["instances_needed"] = needed
     out["max_instances"] = capacity
     return out

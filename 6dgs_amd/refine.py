@@ -131,6 +131,35 @@ def _stack_images(images, dev) -> torch.Tensor:
     return torch.stack([t.to(dev) for t in out])
 
 
+def check_poses(images, c2w, intrinsics, min_views: int = 0):
+    """The poses c2w [V,4,4] and intrinsics K [3,3] or [V,3,3] of `images`, arrays or tensors -> (c2w [V,4,4], K [V,3,3]) as float32:
+    finite poses, one per image, at least min_views of them.  Nothing here needs the GPU."""
+    c2w = torch.as_tensor(np.asarray(c2w) if not torch.is_tensor(c2w) else c2w).detach().float()
+    if c2w.dim() != 3 or tuple(c2w.shape[1:]) != (4, 4) or c2w.shape[0] < min_views:
+        raise ValueError(f"c2w must be [V,4,4] (got {tuple(c2w.shape)})")
+    views = c2w.shape[0]
+    K = torch.as_tensor(np.asarray(intrinsics) if not torch.is_tensor(intrinsics) else intrinsics).detach().float()
+    if tuple(K.shape) == (3, 3):
+        K = K[None].expand(views, 3, 3)
+    if tuple(K.shape) != (views, 3, 3):
+        raise ValueError(f"intrinsics must be [3,3] or [{views},3,3] (got {tuple(K.shape)})")
+    n_images = images.shape[0] if torch.is_tensor(images) else len(images)
+    if n_images != views:
+        raise ValueError(f"{n_images} images for {views} poses")
+    if not torch.isfinite(c2w).all():
+        raise ValueError("c2w must be finite")
+    return c2w, K
+
+
+def posed_views(images, c2w, K, dev, downscale: int, alpha: str, background):
+    """check_poses' (c2w, K) and the images -> (target, rows, width, height) on dev: prepare_target's target and the camera rows [V,16]
+    = w2c rows 0..2, then the intrinsics of the cropped, downscaled image.  The 4 x 4 inversions run on the host, as
+    test.gt_pose_and_intrinsics' does."""
+    target, ox, oy = prepare_target(_stack_images(images, dev), downscale, alpha, background)
+    rows = torch.cat([torch.linalg.inv(c2w.cpu())[:, :3, :].reshape(c2w.shape[0], 12), scaled_intrinsics(K.cpu(), downscale, ox, oy)], dim=1)
+    return target, rows.to(dev).contiguous(), int(target.shape[2]), int(target.shape[1])
+
+
 def _rows_to_c2w(best_rows: torch.Tensor, best_step: torch.Tensor, c2w: torch.Tensor) -> torch.Tensor:
     """The c2w [V,4,4] of the best camera rows (inverted on the host); the input pose itself where the best step is 0."""
     views, dev = c2w.shape[0], c2w.device
@@ -163,29 +192,14 @@ def refine_poses(scene, images, c2w, intrinsics, *, steps: int = 100, lr: float 
     if len(background) != 3:
         raise ValueError("background must have 3 entries")
     steps, downscale = int(steps), int(downscale)
-    c2w = torch.as_tensor(np.asarray(c2w) if not torch.is_tensor(c2w) else c2w).detach().float()
-    if c2w.dim() != 3 or tuple(c2w.shape[1:]) != (4, 4):
-        raise ValueError(f"c2w must be [V,4,4] (got {tuple(c2w.shape)})")
+    c2w, K = check_poses(images, c2w, intrinsics)
     views = c2w.shape[0]
-    K = torch.as_tensor(np.asarray(intrinsics) if not torch.is_tensor(intrinsics) else intrinsics).detach().float()
-    if tuple(K.shape) == (3, 3):
-        K = K[None].expand(views, 3, 3)
-    if tuple(K.shape) != (views, 3, 3):
-        raise ValueError(f"intrinsics must be [3,3] or [{views},3,3] (got {tuple(K.shape)})")
-    n_images = images.shape[0] if torch.is_tensor(images) else len(images)
-    if n_images != views:
-        raise ValueError(f"{n_images} images for {views} poses")
-    if not torch.isfinite(c2w).all():
-        raise ValueError("c2w must be finite")
     tensors, sh_degree = _scene_tensors(scene)
     if not tensors[0].is_cuda:
         raise RuntimeError("6dgs_amd: refine_poses needs the scene on the GPU (no CPU fallback on the product path)")
     dev = tensors[0].device
     tensors = tuple(t.detach() for t in tensors)
-    target, ox, oy = prepare_target(_stack_images(images, dev), downscale, alpha, background)
-    height, width = int(target.shape[1]), int(target.shape[2])
-    # (the two 4 x 4 inversions run on the host, as test.gt_pose_and_intrinsics' does)
-    start = torch.cat([torch.linalg.inv(c2w.cpu())[:, :3, :].reshape(views, 12), scaled_intrinsics(K.cpu(), downscale, ox, oy)], dim=1).to(dev).contiguous()
+    target, start, width, height = posed_views(images, c2w, K, dev, downscale, alpha, background)
     c2w = c2w.to(dev)
     if backend == "fused":
         raw = ops.refine_poses_raw(*tensors, sh_degree, start, width, height, target, steps=steps, lambda_dssim=float(lambda_dssim), lr=float(lr),
