@@ -1,7 +1,7 @@
 // hostcheck.cpp -- HOST instantiation of device_math.h (the per-thread math of the HIP kernels), of dense_layout.h (the index
 // arithmetic of the ray-MLP chain's operand planes), of pose_step.h (the per-view arithmetic of pose refinement) and of adam_step.h
 // (the per-entry arithmetic of fitting a scene's Gaussians) behind a tiny C ABI, so the CPU test-suite can compare the product's arithmetic with the oracle and the
-// golden vectors without a GPU.  Contains no kernels; never used by the product path.
+// golden vectors without a GPU.  densify_rules.h (the per-entry rules of a densification round) is instantiated here too.  Contains no kernels; never used by the product path.
 #include <stdlib.h>
 
 #include "device_math.h"
@@ -10,6 +10,7 @@
 #include "sweep_layout.h"
 #include "pose_step.h"
 #include "adam_step.h"
+#include "densify_rules.h"
 using namespace sdg;
 
 extern "C" {
@@ -224,6 +225,30 @@ int hc_ga_adam(long long n, int n_coef, int step, float* const* p, const float* 
 }
 void hc_ga_reset(float* opacity, long long n, int is_logit, float ceiling) {
   for (long long i = 0; i < n; ++i) opacity[i] = ga::reset_entry(opacity[i], is_logit != 0, ceiling);
+}
+// ---- densify_rules.h: the per-entry rules of densify.hip (tests/test_densify_host.py) ----
+void hc_dn_thresholds(float grad_threshold, float percent_dense, float extent, float min_opacity, int scale_is_log, int opacity_is_logit,
+                      float* out4) {
+  const dn::Thresholds t = dn::thresholds(grad_threshold, percent_dense, extent, min_opacity, scale_is_log, opacity_is_logit, 0, 0);
+  out4[0] = t.grad; out4[1] = t.dense; out4[2] = t.world; out4[3] = t.opacity;
+}
+// sixdgs_densify's classification on the host: cls [n] (0 keep, 1 clone, 2 split), avg [n], flags [4][n] (the candidate of that segment
+// exists and survives the prune), child_xyz [n][2][3] and child_scale [n][3] (of every Gaussian, split or not)
+void hc_dn_round(long long n, const float* xyz, const float* opacity, const float* scale, const float* rot, int scale_is_log, int opacity_is_logit,
+                 const float* grad_accum, const int* denom, const int* max_radii, const float* noise, float grad_threshold, float percent_dense,
+                 float extent, float min_opacity, int prune_big, int screen_size, int* cls, float* avg, int* flags, float* child_xyz,
+                 float* child_scale) {
+  const dn::Thresholds t = dn::thresholds(grad_threshold, percent_dense, extent, min_opacity, scale_is_log, opacity_is_logit, prune_big != 0,
+                                          screen_size);
+  for (long long i = 0; i < n; ++i) {
+    int f[dn::kSegments];
+    cls[i] = dn::candidate_flags(grad_accum[i], denom[i], scale + 3 * i, opacity[i], max_radii[i], scale_is_log != 0, t, f);
+    avg[i] = dn::avg_grad(grad_accum[i], denom[i]);
+    for (int g = 0; g < dn::kSegments; ++g) flags[g * n + i] = f[g];
+    for (int j = 0; j < 2; ++j)
+      dn::child_xyz(xyz + 3 * i, rot + 4 * i, scale + 3 * i, scale_is_log != 0, noise + (i * 2 + j) * 3, child_xyz + (i * 2 + j) * 3);
+    for (int k = 0; k < 3; ++k) child_scale[3 * i + k] = dn::child_scale(scale[3 * i + k], scale_is_log != 0);
+  }
 }
 int hc_dl_const(int which) {
   const int v[] = {dl::kSlabB, dl::kPRow, dl::kGran, dl::kGranSlab, dl::kChunkRun};

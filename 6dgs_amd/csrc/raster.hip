@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "device_math.h"
+#include "pose_step.h"
 #include "render_pass.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -810,6 +811,55 @@ __global__ __launch_bounds__(256) void k_raster_cams_bwd(const int64_t* __restri
   if (tid < 16) d_cams[view * 16 + tid] = acc;
 }
 
+// ---- densification statistics (include/sixdgs.h, sixdgs_densify_stats) -------------------------------------------------------------
+// One lane per Gaussian, views in ascending order: d u, d v of a visible (view, Gaussian) are the sums of its slots' entries 0 and 1
+// in slot order from 0.f -- the bits k_raster_project_bwd chained -- and the three statistics are updated in registers.  Reads both
+// workspaces, writes neither.
+struct StatsArgs {
+  const int64_t *cnt, *offs;
+  const float* slots;
+  const int32_t* radii;
+  float* grad_accum;
+  int32_t *denom, *max_radii;
+  float* grad2d;
+  const int32_t* status;
+  int64_t n, max_instances;
+  int views;
+  float half_w, half_h;
+};
+
+__global__ __launch_bounds__(256) void k_densify_stats(StatsArgs A) {
+  if (A.offs[(int64_t)A.views * A.n] > A.max_instances) return;
+  if (A.status && (*A.status & ps::kStatusCapacity)) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= A.n) return;
+  float acc = A.grad_accum[i];
+  int32_t den = A.denom[i], rad = A.max_radii[i];
+  for (int view = 0; view < A.views; ++view) {
+    const int64_t vi = (int64_t)view * A.n + i;
+    const int64_t cnt = A.cnt[vi];
+    float du = 0.f, dv = 0.f;
+    if (cnt > 0) {
+      const float* __restrict__ sl = A.slots + (size_t)A.offs[vi] * kSlot;
+      for (int64_t t = 0; t < cnt; ++t) {
+        du += sl[t * kSlot];
+        dv += sl[t * kSlot + 1];
+      }
+      const float a = A.half_w * du, b = A.half_h * dv;
+      acc += sqrtf(a * a + b * b);
+      den += 1;
+      rad = max(rad, A.radii[vi]);
+    }
+    if (A.grad2d) {
+      A.grad2d[2 * vi] = du;
+      A.grad2d[2 * vi + 1] = dv;
+    }
+  }
+  A.grad_accum[i] = acc;
+  A.denom[i] = den;
+  A.max_radii[i] = rad;
+}
+
 struct BwdLayout : SdgBump {
   size_t slots, cam_part;
 };
@@ -979,6 +1029,26 @@ int sixdgs_raster_views_backward(const float* xyz, const float* scale, int scale
     hipLaunchKernelGGL(k_raster_cams_bwd, dim3((unsigned)views), dim3(256), 0, s, r.offs + vn, max_instances, cam_part, blocks, d_cams);
     SDG_LAUNCH_OK();
   }
+  return 0;
+}
+
+int sixdgs_densify_stats(int64_t n, int views, int width, int height, int64_t max_instances, const void* fwd_ws, size_t fwd_ws_bytes,
+                         const void* bwd_ws, size_t bwd_ws_bytes, const int32_t* radii, float* grad_accum, int32_t* denom, int32_t* max_radii,
+                         float* grad2d, const int32_t* status, sixdgs_stream_t stream) {
+  SDG_CHECK_ARG(sizes_ok(n, views, width, height, max_instances));
+  if (views == 0 || n == 0) return 0;
+  SDG_CHECK_ARG(fwd_ws && bwd_ws && radii && grad_accum && denom && max_radii);
+  SDG_CHECK_ARG(rp::aligned4(radii) && rp::aligned4(grad_accum) && rp::aligned4(denom) && rp::aligned4(max_radii) && rp::aligned4(grad2d) &&
+                rp::aligned4(status));
+  const Layout F = layout(n, views, width, height, max_instances);
+  const BwdLayout L = bwd_layout(n, views, max_instances);
+  if (fwd_ws_bytes < F.total || bwd_ws_bytes < L.total) return SIXDGS_E_WORKSPACE;
+  SDG_CHECK_ARG(((uintptr_t)fwd_ws & 255) == 0 && ((uintptr_t)bwd_ws & 255) == 0);
+  const char* f = (const char*)fwd_ws;
+  StatsArgs A = {(const int64_t*)(f + F.cnt), (const int64_t*)(f + F.offs), (const float*)((const char*)bwd_ws + L.slots), radii, grad_accum,
+                 denom, max_radii, grad2d, status, n, max_instances, views, 0.5f * (float)width, 0.5f * (float)height};
+  hipLaunchKernelGGL(k_densify_stats, dim3((unsigned)sdg_cdiv(n, 256)), dim3(256), 0, sdg_stream(stream), A);
+  SDG_LAUNCH_OK();
   return 0;
 }
 

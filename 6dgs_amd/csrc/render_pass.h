@@ -66,12 +66,14 @@ inline bool pass_layout(PassLayout& L, int64_t n, int views, int width, int heig
 
 // One pass over `views` camera rows in the workspace w laid out by L: the image, its loss per view against T and -- with grad, which
 // is NULL or w + L.grad -- the loss's gradient, then the rasteriser's backward into the seven d_ outputs; all NULL: no backward.
+// radii (may be NULL): the forward's radii [views][n], for the densification statistics.
 inline int render_pass(const Scene& S, int sh_degree, const float* rows, int views, int width, int height, const Target& T, float lambda,
                        int64_t max_instances, const PassLayout& L, char* w, float* grad, float* d_xyz, float* d_scale, float* d_rot,
-                       float* d_opacity, float* d_f_dc, float* d_f_rest, float* d_rows, sixdgs_stream_t stream) {
+                       float* d_opacity, float* d_f_dc, float* d_f_rest, float* d_rows, sixdgs_stream_t stream,
+                       int32_t* radii = nullptr) {
   float* image = (float*)(w + L.image);
   int st = sixdgs_raster_views(S.xyz, S.scale, S.scale_is_log, S.rot, S.opacity, S.opacity_is_logit, S.f_dc, S.f_rest, sh_degree, S.n_coef, S.n,
-                               rows, views, width, height, S.scale_modifier, S.background, image, nullptr, 3, nullptr, max_instances,
+                               rows, views, width, height, S.scale_modifier, S.background, image, nullptr, 3, radii, max_instances,
                                (int64_t*)(w + L.count), w + L.fwd, L.fwd_bytes, stream, nullptr);
   if (st != 0) return st;
   st = sixdgs_photometric_loss(image, 4, T.data, T.is_u8, T.stride, views, width, height, lambda, nullptr, (float*)(w + L.loss), nullptr, grad,

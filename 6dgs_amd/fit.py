@@ -3,15 +3,26 @@ the given images.
 
     fit_scene(scene, images, c2w, intrinsics, steps=...)      Adam on the six parameter arrays under (1 - lambda) L1 + lambda (1 - SSIM)
 
-This is the loop the reference makes a scene with (train.py:94-122, scene/gaussian_model.py:230-282) WITHOUT densification: the number
-of Gaussians is fixed for a whole fit -- no clone, split or prune, whose statistics the rasteriser's backward does not expose.  What is
-kept: one Adam group per array with its own rate (f_rest at feature_lr / 20), the exponentially decaying position rate, the SH degree
-that steps up every sh_up_every iterations, the periodic opacity reset, and the sampling of views without replacement.
+This is the loop the reference makes a scene with (train.py:94-184, scene/gaussian_model.py:230-282 and :422-632): one Adam group
+per array with its own rate (f_rest at feature_lr / 20), the exponentially decaying position rate, the SH degree that steps up every
+sh_up_every iterations, the periodic opacity reset, the sampling of views without replacement and -- with densify=... -- adaptive
+density control: the statistics of every pass (ops.densify_stats), and every `interval` iterations a round of clone, split and prune
+(ops.densify) that changes the number of Gaussians.  Without densify the number is fixed for the whole fit.
+
+Deviations from the reference, with densify: a round's iteration makes NO Adam update (in the reference the freshly made parameters
+carry no gradient, so its optimiser steps nothing there either) and Adam's counter counts the updates actually made; the opacity
+reset follows the Adam update of its iteration, as it does without densify (the reference resets first and so skips the opacity's
+update on that iteration); screen_size defaults to 0, because the reference zeroes max_radii2D before it prunes and its screen-size
+test never fires; the per-pass gradient statistic is the norm of the NDC-position gradient, (0.5 W du, 0.5 H dv), as include/sixdgs.h
+defines it; the split's normals come from torch.randn on the host, seeded from `seed` and the round number, for both backends.
 
 Two backends run the same loop.  "torch" (the default, the reference arm): torch.optim.Adam over six groups, autograd.raster_views and
 autograd.photometric_loss.  "fused": the whole loop as one library call (ops.fit_scene_raw -> sixdgs_fit_scene: the same kernels per
 step, Adam and the reset as HIP kernels, nothing read back until the end), so its iterates differ from the torch ones by Adam's
-rounding order only.
+rounding order only.  With densify the fused run is cut into segments that end at the rounds' iterations: one
+sixdgs_fit_scene_steps call per segment, one sixdgs_densify call per round and ONE 8-byte read of n_out behind it -- the only
+read-back, at most once per `interval` steps; the torch arm runs the same schedule with torch.optim.Adam, the raw render ops (so that
+ops.densify_stats can follow the backward) and the round in plain torch ops (densify_torch).
 """
 from __future__ import annotations
 
@@ -62,6 +73,122 @@ def reset_opacity_(opacity: torch.Tensor, ceiling: float) -> None:
     opacity.copy_(torch.log(o / (1.0 - o)))
 
 
+DENSIFY_DEFAULTS = {"from_iter": 500, "until_iter": 15000, "interval": 100, "grad_threshold": 2e-4, "percent_dense": 0.01, "min_opacity": 0.005,
+                    "extent": None, "prune_big_after": 3000, "screen_size": 0, "reset_at_from_iter": False, "seed": 0}
+
+
+def densify_options(densify) -> dict:
+    """fit_scene's densify argument -- a dict (or an object with attributes) naming some of DENSIFY_DEFAULTS' options -- checked and
+    completed with the reference's defaults.  extent None means cameras_extent of the fit's poses."""
+    if not isinstance(densify, dict):
+        densify = {k: getattr(densify, k) for k in DENSIFY_DEFAULTS if hasattr(densify, k)}
+    unknown = sorted(set(densify) - set(DENSIFY_DEFAULTS))
+    if unknown:
+        raise ValueError(f"densify: unknown options {unknown} (known: {sorted(DENSIFY_DEFAULTS)})")
+    o = {**DENSIFY_DEFAULTS, **densify}
+    for k in ("from_iter", "until_iter", "prune_big_after", "screen_size", "seed"):
+        o[k] = _int_at_least(o[k], 0, f"densify[{k!r}]")
+    o["interval"] = _int_at_least(o["interval"], 1, "densify['interval']")
+    for k in ("grad_threshold", "percent_dense") + (("extent",) if o["extent"] is not None else ()):
+        if isinstance(o[k], bool) or not (0.0 < float(o[k]) < float("inf")):
+            raise ValueError(f"densify[{k!r}] must be positive and finite (got {o[k]!r})")
+        o[k] = float(o[k])
+    if isinstance(o["min_opacity"], bool) or not (0.0 <= float(o["min_opacity"]) < 1.0):
+        raise ValueError(f"densify['min_opacity'] must be in [0, 1) (got {o['min_opacity']!r})")
+    o["min_opacity"], o["reset_at_from_iter"] = float(o["min_opacity"]), bool(o["reset_at_from_iter"])
+    return o
+
+
+def cameras_extent(c2w) -> float:
+    """The reference's cameras_extent (scene/datasets_utils.py:7-25): 1.1 x the largest distance of a camera centre from their mean."""
+    centres = np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, dtype=np.float64)[:, :3, 3]
+    return float(1.1 * np.max(np.linalg.norm(centres - centres.mean(axis=0, keepdims=True), axis=1)))
+
+
+def densify_plan(steps: int, densify, opacity_reset_every: int = 0, opacity_moves: bool = True) -> dict:
+    """What happens at iteration it = s + 1 of a fit, as bool arrays [steps] -- a pure host function.  densify None: every step
+    updates, none accumulates or densifies, and the opacity resets after every opacity_reset_every-th iteration (today's loop).
+    Otherwise, after train.py:152-184: while it < until_iter the pass's statistics are accumulated ("stats"), a round runs when
+    it > from_iter and it % interval == 0 ("round"; that step makes no update, and prunes big Gaussians when it > prune_big_after:
+    "prune_big"), and the opacity is reset when it % opacity_reset_every == 0 or, with reset_at_from_iter, it == from_iter ("reset").
+    Resets are dropped when the opacity does not move."""
+    it = np.arange(int(steps)) + 1
+    every = int(opacity_reset_every)
+    periodic = (it % every == 0) if every > 0 else np.zeros(int(steps), bool)
+    if densify is None:
+        none = np.zeros(int(steps), bool)
+        plan = {"update": ~none, "stats": none, "round": none.copy(), "prune_big": none.copy(), "reset": periodic}
+    else:
+        o = densify_options(densify)
+        active = it < o["until_iter"]
+        rounds = active & (it > o["from_iter"]) & (it % o["interval"] == 0)
+        reset = active & (periodic | (o["reset_at_from_iter"] & (it == o["from_iter"])))
+        plan = {"update": ~rounds, "stats": active, "round": rounds, "prune_big": it > o["prune_big_after"], "reset": reset}
+    if not opacity_moves:
+        plan["reset"] = np.zeros(int(steps), bool)
+    return plan
+
+
+def round_noise(n: int, seed: int, round_no: int, device) -> torch.Tensor:
+    """The standard normals [n,2,3] of round round_no (from 0) of a fit seeded with `seed`: the same numbers for both backends."""
+    gen = torch.Generator().manual_seed(int(seed) * 1000003 + int(round_no))
+    return torch.randn((int(n), 2, 3), generator=gen).to(device)
+
+
+def _rotmat(q: torch.Tensor) -> torch.Tensor:
+    """device_math.h's quat_to_rotmat in torch: q = (w, x, y, z) [n,4], normalised twice -> [n,3,3]."""
+    q = q / torch.clamp(q.norm(dim=1, keepdim=True), min=1e-12)
+    r, x, y, z = (q / q.norm(dim=1, keepdim=True)).unbind(1)
+    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y), 2 * (x * y + r * z), 1 - 2 * (x * x + z * z),
+                        2 * (y * z - r * x), 2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+
+
+def densify_torch(params: dict, state: dict, stats: dict, noise: torch.Tensor, *, grad_threshold, percent_dense, extent, min_opacity,
+                  prune_big, screen_size: int = 0, scale_is_log: bool = True, opacity_is_logit: bool = True):
+    """ops.densify in plain torch ops, after the reference's densify_and_clone, densify_and_split, densification_postfix and
+    prune_points (masks, cat, indexing): the torch arm's round, and the GPU tests' second restatement.  params: the six arrays by
+    name; state: name -> (exp_avg, exp_avg_sq) in the arrays' shapes, or None for a group the optimiser holds no state of -- the
+    surgery of cat_tensors_to_optimizer / _prune_optimizer: zeros for what is new, the mask for what is pruned; stats:
+    ops.densify_stats_state's dict; noise [n,2,3].  The thresholds are ops.densify_thresholds': compared in the stored domain.
+    Returns (new params, new state, (n_out, clones, split sources, candidates pruned))."""
+    t = ops.densify_thresholds(grad_threshold=grad_threshold, percent_dense=percent_dense, extent=extent, min_opacity=min_opacity,
+                               scale_is_log=scale_is_log, opacity_is_logit=opacity_is_logit)
+    n = params["xyz"].shape[0]
+    denom = stats["denom"]
+    avg = torch.where(denom > 0, stats["grad_accum"] / denom.float(), torch.zeros_like(stats["grad_accum"]))
+    scale = params["scale"]
+    big = scale.max(dim=1).values > t["dense"]
+    selected = avg >= t["grad"]
+    clone, split = selected & ~big, selected & big
+    # densify_and_clone, then densify_and_split (which sees a zero gradient for the clones), then its prune of the split sources
+    src = torch.cat([torch.nonzero(~split)[:, 0], torch.nonzero(clone)[:, 0], torch.nonzero(split)[:, 0], torch.nonzero(split)[:, 0]])
+    n_keep, n_clone, n_split = n - int(split.sum()), int(clone.sum()), int(split.sum())
+    new = {k: v[src] for k, v in params.items()}
+    first_child = n_keep + n_clone
+    sigma = torch.exp(scale[split]) if scale_is_log else scale[split]
+    rot = _rotmat(params["rot"][split])
+    for j in range(2):
+        rows = slice(first_child + j * n_split, first_child + (j + 1) * n_split)
+        new["xyz"][rows] = torch.bmm(rot, (sigma * noise[split, j]).unsqueeze(-1)).squeeze(-1) + params["xyz"][split]
+        new["scale"][rows] = scale[split] - 0.470003629 if scale_is_log else scale[split] / torch.tensor(1.6, device=scale.device)
+    original = torch.arange(src.shape[0], device=src.device) < n_keep
+    radii = torch.where(original, stats["max_radii"][src], torch.zeros_like(src, dtype=torch.int32))
+    # prune_points on the candidates' own stored values
+    prune = new["opacity"].reshape(-1) < t["opacity"]
+    if prune_big:
+        prune = prune | (new["scale"].max(dim=1).values > t["world"])
+        if screen_size > 0:
+            prune = prune | (radii > screen_size)
+    keep = ~prune
+    new = {k: v[keep] for k, v in new.items()}
+    new_state = {}
+    for k, mv in state.items():
+        new_state[k] = None if mv is None else tuple(torch.where(original.reshape(-1, *[1] * (x.dim() - 1)), x[src], torch.zeros_like(x[src]))[keep]
+                                                    for x in mv)
+    n_out = int(keep.sum())
+    return new, new_state, (n_out, n_clone, n_split, n + n_clone + n_split - n_out)
+
+
 def _int_at_least(x, low, name):
     if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) < low:
         raise ValueError(f"{name} must be an integer >= {low} (got {x!r})")
@@ -79,7 +206,7 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
               spatial_lr_scale: float = 1.0, feature_lr: float = 2.5e-3, opacity_lr: float = 0.05, scaling_lr: float = 5e-3,
               rotation_lr: float = 1e-3, eps: float = 1e-15, lambda_dssim: float = 0.2, sh_degree_start=None, sh_up_every: int = 1000,
               opacity_reset_every: int = 0, reset_ceiling: float = 0.01, downscale: int = 1, alpha: str = "ignore",
-              background=(1.0, 1.0, 1.0), seed: int = 0, schedule=None):
+              background=(1.0, 1.0, 1.0), seed: int = 0, schedule=None, densify=None):
     """Fit `scene` (a GaussianScene on the GPU) to the posed `images` (uint8 [H,W,3|4] arrays or GPU tensors of one size) seen from
     c2w [V,4,4] with intrinsics K [3,3] or [V,3,3]: `steps` Adam steps, each on `batch` views, objective
     photometric_loss(raster_views(...)).sum() at 1 / downscale of the resolution.  Returns (new_scene, report): new_scene is a NEW
@@ -87,7 +214,15 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
     the step's update), views [steps, batch] (int64) and status (int32 [1]; 0 = fine, bit 0: a gradient entry was not finite and was
     left out -- the fused backend alone reports it).
 
-    The number of Gaussians is fixed: no densification.  groups: the arrays that move, among ("xyz", "f_dc", "f_rest", "opacity",
+    densify=None: the number of Gaussians is fixed -- today's loop, bit for bit.  Otherwise a dict (or an object with attributes) of
+    DENSIFY_DEFAULTS' options, the reference's defaults: statistics are accumulated while it < until_iter (it = step + 1); when
+    it > from_iter and it % interval == 0 the step makes NO Adam update (Adam's counter counts the updates actually made) and a round
+    of clone / split / prune runs with grad_threshold, percent_dense, min_opacity, extent (None: cameras_extent(c2w)), big Gaussians
+    pruned when it > prune_big_after, screen_size (0: off, the reference's behaviour), the split's normals from torch.randn seeded from
+    densify's seed and the round number; the statistics are zeroed after a round; the opacity is reset, after the step's update or
+    round, while it < until_iter when it % opacity_reset_every == 0 or, with reset_at_from_iter, it == from_iter.  report then gains
+    rounds (int64 [R,6] on the host, one row per round: iteration, n before, clones, split sources, candidates pruned, n after) and
+    n_final (= len(new_scene)).  The fused backend reads n_out (8 bytes) once per round and nothing else until the end.  groups: the arrays that move, among ("xyz", "f_dc", "f_rest", "opacity",
     "scale", "rot"); the others are copied unchanged.  Rates: the reference's defaults; f_rest learns at feature_lr / 20; the position
     rate is position_lr(s + 1, ...) at step s.  sh_degree_start=None renders at the scene's active degree throughout; otherwise the
     degree starts there and rises by one every sh_up_every iterations up to the scene's maximum (the new scene's active degree is the
@@ -123,6 +258,8 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
         raise ValueError("background must have 3 entries")
     if not isinstance(scene, GaussianScene):
         raise ValueError(f"scene must be a GaussianScene (got {type(scene).__name__})")
+    if densify is not None:
+        densify_options(densify)
     max_degree = int(scene.max_sh_degree)
     if sh_degree_start is not None:
         sh_degree_start = _int_at_least(sh_degree_start, 0, "sh_degree_start")
@@ -152,16 +289,25 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
         degrees = np.full(steps, int(scene.active_sh_degree), np.int32)
     else:       # the reference raises the degree at the START of every sh_up_every-th iteration
         degrees = np.minimum(sh_degree_start + (np.arange(steps) + 1) // sh_up_every, max_degree).astype(np.int32)
-    resets = np.zeros(steps, bool)
-    if opacity_reset_every > 0 and "opacity" in groups:
-        resets = (np.arange(steps) + 1) % opacity_reset_every == 0
+    plan = densify_plan(steps, densify, opacity_reset_every, "opacity" in groups)
+    resets = plan["reset"]
     views_t = torch.from_numpy(views.astype(np.int64)).to(dev)
     eps, lam = rates["eps"], float(lambda_dssim)
-    if backend == "fused":
+    if densify is not None:
+        opts = densify_options(densify)
+        if opts["extent"] is None:
+            opts["extent"] = cameras_extent(c2w)
+        run = _fit_densify_fused if backend == "fused" else _fit_densify_torch
+        params, history, status, rounds = run(params, cams, width, height, target, views_t, lrs, degrees, plan, opts, groups, lam, eps,
+                                              float(reset_ceiling), background)
+        extra = {"rounds": rounds, "n_final": int(params["xyz"].shape[0])}
+    elif backend == "fused":
+        extra = {}
         raw = ops.fit_scene_raw(params, cams, width, height, target, views=views, lrs=lrs, sh_degrees=degrees, resets=resets, groups=groups,
                                 lambda_dssim=lam, eps=eps, reset_ceiling=float(reset_ceiling), background=background)
         history, status = raw["history"], raw["status"]
     else:
+        extra = {}
         history = torch.empty(steps, batch, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         for k in groups:
@@ -189,4 +335,135 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
     new.active_sh_degree = int(degrees[-1])
     for k, a in _SCENE_ATTR.items():
         setattr(new, a, params[k])
-    return new, {"loss_history": history, "views": views_t, "status": status}
+    return new, {"loss_history": history, "views": views_t, "status": status, **extra}
+
+
+_ORDER = ops.SCENE_ARRAYS
+
+
+def _round_kw(opts, prune_big):
+    return dict(grad_threshold=opts["grad_threshold"], percent_dense=opts["percent_dense"], extent=opts["extent"],
+                min_opacity=opts["min_opacity"], prune_big=bool(prune_big), screen_size=opts["screen_size"])
+
+
+def _rounds_table(rows, dev):
+    """[(iteration, n before, counts int64 [4] on the device)] -> int64 [R,6] on the host: iteration, n before, clones, split sources,
+    candidates pruned, n after."""
+    if not rows:
+        return torch.zeros(0, 6, dtype=torch.int64)
+    counts = torch.stack([torch.as_tensor(c, dtype=torch.int64, device=dev) for _, _, c in rows]).cpu()
+    head = torch.tensor([[it, n] for it, n, _ in rows], dtype=torch.int64)
+    return torch.cat([head, counts[:, 1:], counts[:, :1]], dim=1)
+
+
+def _fit_densify_fused(start, cams, width, height, target, views_t, lrs, degrees, plan, opts, groups, lam, eps, ceiling, background):
+    """fit_scene's fused backend with densification: segments of sixdgs_fit_scene_steps that end at the rounds' iterations, one
+    sixdgs_densify per round into buffers of 2 n rows (so a round never retries) and one 8-byte read of n_out behind it.  status and the
+    largest instance count are read once at the end; when the capacity was too small the whole fit runs once more, from the start,
+    with 5/4 of what it needed as every segment's floor."""
+    steps, batch = views_t.shape
+    dev = cams.device
+    views = views_t.cpu().numpy().astype(np.int32)
+    ends = [int(s) + 1 for s in np.nonzero(plan["round"])[0]]
+    if not ends or ends[-1] != steps:
+        ends.append(steps)
+    floor = 0
+    for attempt in range(2):
+        params = {k: v.clone() for k, v in start.items()}
+        n = params["xyz"].shape[0]
+        state = ops.gaussian_adam_state(params)
+        state["instances_needed"] = torch.zeros(1, dtype=torch.int64, device=dev)
+        stats = ops.densify_stats_state(n, dev)
+        history = torch.empty(steps, batch, device=dev)
+        rows, first, updates_made = [], 0, 0
+        for end in ends:
+            seg = slice(first, end)
+            is_round = bool(plan["round"][end - 1])
+            seg_resets = plan["reset"][seg].copy()
+            reset_after_round = is_round and bool(seg_resets[-1])
+            if is_round:
+                seg_resets[-1] = False          # the round comes first, as in the reference: the reset follows it below
+            history[seg] = ops.fit_scene_steps_raw(params, cams, width, height, target, state, views=views[seg], lrs=lrs[seg],
+                                                   sh_degrees=degrees[seg], resets=seg_resets, updates=plan["update"][seg],
+                                                   stats_steps=plan["stats"][seg], stats=stats, first_adam_step=updates_made, groups=groups,
+                                                   lambda_dssim=lam, eps=eps, reset_ceiling=ceiling, background=background,
+                                                   max_instances=max(ops.raster_instances_estimate(n, batch), floor))
+            updates_made += int(plan["update"][seg].sum())
+            if is_round:
+                noise = round_noise(n, opts["seed"], len(rows), dev)
+                params, new_state, counts = ops.densify(params, state, stats, noise, **_round_kw(opts, plan["prune_big"][end - 1]))
+                rows.append((end, n, counts))
+                n = params["xyz"].shape[0]
+                state = {**new_state, "instances_needed": state["instances_needed"]}
+                stats = ops.densify_stats_state(n, dev)
+                if reset_after_round and n > 0:
+                    sl = ops.gaussian_adam_slices(n, 1 + params["f_rest"].shape[1])["opacity"]
+                    ops.opacity_reset(params["opacity"], state["m"][sl], state["v"][sl], ceiling=ceiling)
+            first = end
+        flags = torch.cat([state["status"].to(torch.int64), state["instances_needed"]]).cpu()
+        if not int(flags[0]) & ops.FIT_STATUS_CAPACITY:
+            break
+        if attempt == 1 or int(flags[1]) > ops.RASTER_MAX_INSTANCES:
+            raise RuntimeError(f"6dgs_amd: fit_scene still needs {int(flags[1])} tile instances after {attempt + 1} runs (limit 2^31 - 1): "
+                               "fit fewer views at once")
+        floor = ops._grown(int(flags[1]))
+    return params, history, state["status"], _rounds_table(rows, dev)
+
+
+def _fit_densify_torch(start, cams, width, height, target, views_t, lrs, degrees, plan, opts, groups, lam, eps, ceiling, background):
+    """fit_scene's torch backend with densification, the reference arm: the same schedule with torch.optim.Adam; the render pass goes
+    through the raw ops so that ops.densify_stats can follow the backward; the round is densify_torch, with the optimiser-state surgery
+    of the reference's cat_tensors_to_optimizer / _prune_optimizer."""
+    steps, batch = views_t.shape
+    dev = cams.device
+    params = {k: v.clone() for k, v in start.items()}
+    n = params["xyz"].shape[0]
+    opt = torch.optim.Adam([{"params": [params[k]], "lr": float(lrs[0][GROUPS.index(k)]), "name": k} for k in groups], lr=0.0, eps=eps)
+    stats = ops.densify_stats_state(n, dev)
+    history = torch.empty(steps, batch, device=dev)
+    rows = []
+    want = tuple(k for k in _ORDER if k in groups)
+    for s in range(steps):
+        for group in opt.param_groups:
+            group["lr"] = float(np.float32(lrs[s][GROUPS.index(group["name"])]))
+        idx = views_t[s]
+        rows_s, tgt = cams[idx].contiguous(), target[idx].contiguous()
+        scene = [params[k] for k in _ORDER]
+        image, radii, fwd = ops.raster_views(*scene, int(degrees[s]), rows_s, width, height, want_float=True, want_u8=False, want_radii=True,
+                                             want_state=True, background=background)
+        loss, grad = ops.photometric_loss(image, tgt, lambda_dssim=lam, want_grad=True)
+        history[s] = loss
+        if n > 0:
+            bwd_ws = torch.empty(max(ops.raster_views_backward_workspace_bytes(n, batch, width, height, fwd[1]), 1), dtype=torch.uint8, device=dev)
+            grads = ops.raster_views_backward(*scene, int(degrees[s]), rows_s, width, height, grad, fwd, background=background, want=want,
+                                              workspace=bwd_ws)
+            if plan["stats"][s]:
+                ops.densify_stats(fwd, bwd_ws, radii, stats, width, height)
+            if plan["update"][s]:
+                for k, g in zip(ops.RASTER_GRADIENTS, grads):
+                    if g is not None:
+                        params[k].grad = g
+                opt.step()
+                opt.zero_grad(set_to_none=True)
+        if plan["round"][s]:
+            held = {k: opt.state.get(params[k]) for k in groups}
+            state = {k: (None if not held[k] else (held[k]["exp_avg"], held[k]["exp_avg_sq"])) for k in groups}
+            new, new_state, counts = densify_torch(params, state, stats, round_noise(n, opts["seed"], len(rows), dev),
+                                                   **_round_kw(opts, plan["prune_big"][s]))
+            rows.append((s + 1, n, counts))
+            for group in opt.param_groups:
+                k = group["name"]
+                opt.state.pop(params[k], None)
+                group["params"][0] = new[k]
+                if held[k]:
+                    held[k]["exp_avg"], held[k]["exp_avg_sq"] = new_state[k]
+                    opt.state[new[k]] = held[k]
+            params, n = new, new["xyz"].shape[0]
+            stats = ops.densify_stats_state(n, dev)
+        if plan["reset"][s] and n > 0:
+            reset_opacity_(params["opacity"], ceiling)
+            held = opt.state.get(params["opacity"])
+            if held:
+                held["exp_avg"].zero_()
+                held["exp_avg_sq"].zero_()
+    return params, history, torch.zeros(1, dtype=torch.int32, device=dev), _rounds_table(rows, dev)

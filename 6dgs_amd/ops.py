@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import math
 import os
 import threading
 from typing import Optional, Tuple
@@ -835,20 +836,9 @@ def fit_scene_workspace_bytes(n: int, n_coef: int, batch: int, width: int, heigh
     return int(_lib.load().sixdgs_fit_scene_workspace_bytes(int(n), int(n_coef), int(batch), int(width), int(height), int(max_instances)))
 
 
-@_on_device
-def fit_scene_raw(params: dict, cams: torch.Tensor, width: int, height: int, target: torch.Tensor, *, views, lrs, sh_degrees, resets=None,
-                  groups=FIT_GROUPS, lambda_dssim: float = 0.2, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-15,
-                  reset_ceiling: float = 0.01, scale_modifier: float = 1.0, background=(1.0, 1.0, 1.0), scale_is_log: bool = True,
-                  opacity_is_logit: bool = True, max_instances: Optional[int] = None, retry: bool = True) -> dict:
-    """Fit the six arrays of `params` (a dict by FIT_GROUPS' names, UPDATED IN PLACE) to posed views as ONE library call
-    (sixdgs_fit_scene in include/sixdgs.h): per step a render of the step's views, the loss, the backward, one Adam step and -- where
-    asked -- the opacity reset, enqueued without a host read.  cams [V,16]; target fp32 [V,height,width,3|4] or uint8 [V,height,width,3];
-    views int [steps,batch] (indices into cams, duplicates allowed), lrs [steps,6] in FIT_GROUPS' order, sh_degrees [steps],
-    resets [steps] (None: never); groups: the names that move (the others stay bit for bit and get no gradient).
-    Returns a dict: history [steps,batch], m, v, status (int32 [1]; bit 0: a gradient entry was not finite and was left out, bit 1: the
-    instance capacity was too small), instances_needed (int) and max_instances (int: the capacity of the run returned).  The call
-    runs with raster_instances_estimate's capacity (or max_instances), reads status and instances_needed once at the end, and -- with
-    retry -- on bit 1 puts back the copy of the scene it took before the call and runs once more with 5/4 of the needed capacity."""
+def _fit_args(params, cams, width, height, target, views, lrs, sh_degrees, resets, groups, lambda_dssim, beta1, beta2, eps, reset_ceiling,
+              scale_modifier, background, opacity_is_logit):
+    """The checks fit_scene_raw and fit_scene_steps_raw share, before _need_gpu -> the arguments in the form the C call takes them."""
     n, n_coef = _fit_params(params)
     lam = _lambda(lambda_dssim)
     _check_fit_hyper(beta1, beta2, eps)
@@ -882,6 +872,27 @@ def fit_scene_raw(params: dict, cams: torch.Tensor, width: int, height: int, tar
     if bool(reset_t.any()) and not opacity_is_logit:
         raise ValueError("an opacity reset needs opacity_is_logit")
     target, target_is_u8, target_stride = _target_args(target, n_views, height, width)
+    return (n, n_coef, lam, groups, cams, width, height, n_views, steps, batch, view_t, lr_t, deg_t, reset_t, target, target_is_u8,
+            target_stride)
+
+
+@_on_device
+def fit_scene_raw(params: dict, cams: torch.Tensor, width: int, height: int, target: torch.Tensor, *, views, lrs, sh_degrees, resets=None,
+                  groups=FIT_GROUPS, lambda_dssim: float = 0.2, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-15,
+                  reset_ceiling: float = 0.01, scale_modifier: float = 1.0, background=(1.0, 1.0, 1.0), scale_is_log: bool = True,
+                  opacity_is_logit: bool = True, max_instances: Optional[int] = None, retry: bool = True) -> dict:
+    """Fit the six arrays of `params` (a dict by FIT_GROUPS' names, UPDATED IN PLACE) to posed views as ONE library call
+    (sixdgs_fit_scene in include/sixdgs.h): per step a render of the step's views, the loss, the backward, one Adam step and -- where
+    asked -- the opacity reset, enqueued without a host read.  cams [V,16]; target fp32 [V,height,width,3|4] or uint8 [V,height,width,3];
+    views int [steps,batch] (indices into cams, duplicates allowed), lrs [steps,6] in FIT_GROUPS' order, sh_degrees [steps],
+    resets [steps] (None: never); groups: the names that move (the others stay bit for bit and get no gradient).
+    Returns a dict: history [steps,batch], m, v, status (int32 [1]; bit 0: a gradient entry was not finite and was left out, bit 1: the
+    instance capacity was too small), instances_needed (int) and max_instances (int: the capacity of the run returned).  The call
+    runs with raster_instances_estimate's capacity (or max_instances), reads status and instances_needed once at the end, and -- with
+    retry -- on bit 1 puts back the copy of the scene it took before the call and runs once more with 5/4 of the needed capacity."""
+    (n, n_coef, lam, groups, cams, width, height, n_views, steps, batch, view_t, lr_t, deg_t, reset_t, target, target_is_u8,
+     target_stride) = _fit_args(params, cams, width, height, target, views, lrs, sh_degrees, resets, groups, lambda_dssim, beta1, beta2, eps,
+                                reset_ceiling, scale_modifier, background, opacity_is_logit)
     capacity = _capacity(max_instances, n, batch)
     arrays = [params[k] for k in SCENE_ARRAYS]
     _need_gpu(*arrays, cams, target)
@@ -920,6 +931,221 @@ def fit_scene_raw(params: dict, cams: torch.Tensor, width: int, height: int, tar
     out["instances_needed"] = needed
     out["max_instances"] = capacity
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# adaptive density control below the C ABI
+# ---------------------------------------------------------------------------------------------
+DENSIFY_STATS = (("grad_accum", torch.float32), ("denom", torch.int32), ("max_radii", torch.int32))
+
+
+def densify_stats_state(n: int, device) -> dict:
+    """The statistics a densification round reads, zeroed: grad_accum float32 [n], denom int32 [n], max_radii int32 [n]."""
+    return {k: torch.zeros(int(n), dtype=dt, device=device) for k, dt in DENSIFY_STATS}
+
+
+def _check_stats(stats, n):
+    if not isinstance(stats, dict):
+        raise ValueError("stats must be the dict of ops.densify_stats_state")
+    for k, dt in DENSIFY_STATS:
+        t = stats.get(k)
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"stats[{k!r}] must be a contiguous {dt} [{n}] tensor (ops.densify_stats_state makes the dict)")
+
+
+def densify_thresholds(*, grad_threshold, percent_dense, extent, min_opacity, scale_is_log: bool = True, opacity_is_logit: bool = True) -> dict:
+    """The thresholds of a round in the domain the arrays are stored in, as sixdgs_densify forms them: each converted once, in double,
+    from the float32 arguments and rounded to float32.  Keys grad, dense, world, opacity (Python floats holding float32 values)."""
+    f = lambda x: C.c_float(float(x)).value
+    dense, world, p = f(percent_dense) * f(extent), 0.1 * f(extent), f(min_opacity)
+    if not (f(grad_threshold) > 0.0 and dense > 0.0 and 0.0 <= p < 1.0) or not all(math.isfinite(x) for x in (f(grad_threshold), dense)):
+        raise ValueError("grad_threshold, percent_dense and extent must be positive and finite, min_opacity in [0, 1)")
+    if scale_is_log:
+        dense, world = math.log(dense), math.log(world)
+    if opacity_is_logit:
+        p = math.log(p / (1.0 - p)) if p > 0.0 else float("-inf")
+    return {"grad": f(grad_threshold), "dense": f(dense), "world": f(world), "opacity": f(p)}
+
+
+@_on_device
+def densify_stats(state, bwd_workspace: torch.Tensor, radii: torch.Tensor, stats: dict, width: int, height: int, *, want_grad2d: bool = False,
+                  status: Optional[torch.Tensor] = None):
+    """Accumulate the densification statistics of one render pass IN PLACE (sixdgs_densify_stats in include/sixdgs.h): state = the
+    (workspace, capacity) pair of raster_views(..., want_state=True, want_radii=True), bwd_workspace = the tensor
+    raster_views_backward(..., workspace=...) ran in on the same arguments, radii int32 [V,N] the forward's.  Per visible (view,
+    Gaussian): grad_accum += the norm of the NDC-position gradient, denom += 1, max_radii = max(max_radii, radius).  Returns grad2d
+    float32 [V,N,2] -- the raw (du, dv), zeros where invisible -- with want_grad2d, else None."""
+    if (not isinstance(state, (tuple, list)) or len(state) != 2 or not torch.is_tensor(state[0])
+            or not 1 <= int(state[1]) <= RASTER_MAX_INSTANCES):
+        raise ValueError("state must be the (workspace, capacity) pair of raster_views(..., want_state=True)")
+    fwd_ws, capacity = state[0], int(state[1])
+    if int(width) < 1 or int(height) < 1:
+        raise ValueError(f"width and height must be positive (got {width} x {height})")
+    if not torch.is_tensor(radii) or radii.dim() != 2 or radii.dtype != torch.int32 or not radii.is_contiguous():
+        raise ValueError("radii must be a contiguous int32 [views,n] tensor")
+    if not torch.is_tensor(bwd_workspace):
+        raise ValueError("bwd_workspace must be the workspace tensor of raster_views_backward")
+    views, n = int(radii.shape[0]), int(radii.shape[1])
+    _check_stats(stats, n)
+    if status is not None and (not torch.is_tensor(status) or tuple(status.shape) != (1,) or status.dtype != torch.int32):
+        raise ValueError("status must be an int32 [1] tensor")
+    _need_gpu(fwd_ws, bwd_workspace, radii, *[stats[k] for k, _ in DENSIFY_STATS], status)
+    grad2d = torch.zeros(views, n, 2, device=radii.device) if want_grad2d else None
+    check(_lib.load().sixdgs_densify_stats(n, views, int(width), int(height), capacity, _p(fwd_ws), fwd_ws.numel() * fwd_ws.element_size(),
+                                           _p(bwd_workspace), bwd_workspace.numel() * bwd_workspace.element_size(), _p(radii),
+                                           _p(stats["grad_accum"]), _p(stats["denom"]), _p(stats["max_radii"]), _p(grad2d), _p(status),
+                                           _stream()),
+          "densify_stats")
+    return grad2d
+
+
+def densify_workspace_bytes(n: int) -> int:
+    return int(_lib.load().sixdgs_densify_workspace_bytes(int(n)))
+
+
+def densify_buffers(params: dict, n_cap: int) -> dict:
+    """Output buffers of n_cap rows for densify_raw: the six arrays in the shapes of `params`, m and v of n_cap (11 + 3 n_coef) floats."""
+    n, n_coef = _fit_params(params)
+    out = {k: torch.empty((int(n_cap), *params[k].shape[1:]), device=params[k].device) for k in FIT_GROUPS}
+    for k in ("m", "v"):
+        out[k] = torch.empty(int(n_cap) * (11 + 3 * n_coef), device=params["xyz"].device)
+    return out
+
+
+def densify_raw(params: dict, state: dict, stats: dict, noise: torch.Tensor, out: dict, *, grad_threshold: float, percent_dense: float,
+                extent: float, min_opacity: float, prune_big: bool, screen_size: int = 0, scale_is_log: bool = True,
+                opacity_is_logit: bool = True, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One densification round as ONE library call, out of place and without a host read (sixdgs_densify in include/sixdgs.h): from
+    params (dict by FIT_GROUPS' names), state (gaussian_adam_state's dict: m, v, status), stats (densify_stats_state's dict) and noise
+    float32 [n,2,3] (standard normals) into `out` (densify_buffers' dict; its row count is the capacity).  Returns counts, int64 [4] on
+    the device: n_out, clones, split sources, candidates pruned.  The first n_out rows of the six arrays and the first
+    n_out (11 + 3 n_coef) floats of out["m"], out["v"] are written, nothing else; if n_out exceeds the capacity only counts and bit 1
+    of state["status"] are."""
+    _fit_params(params)
+    return _densify_raw(params["xyz"], params, state, stats, noise, out, grad_threshold, percent_dense, extent, min_opacity, prune_big,
+                        screen_size, scale_is_log, opacity_is_logit, workspace)
+
+
+@_on_device
+def _densify_raw(anchor, params, state, stats, noise, out, grad_threshold, percent_dense, extent, min_opacity, prune_big, screen_size,
+                 scale_is_log, opacity_is_logit, workspace):
+    n, n_coef = _fit_params(params)
+    densify_thresholds(grad_threshold=grad_threshold, percent_dense=percent_dense, extent=extent, min_opacity=min_opacity,
+                       scale_is_log=scale_is_log, opacity_is_logit=opacity_is_logit)
+    if isinstance(screen_size, bool) or int(screen_size) != screen_size or int(screen_size) < 0:
+        raise ValueError(f"screen_size must be a non-negative integer (got {screen_size})")
+    _check_stats(stats, n)
+    size = n * (11 + 3 * n_coef)
+    for name in ("m", "v"):
+        t = state.get(name) if isinstance(state, dict) else None
+        if not torch.is_tensor(t) or tuple(t.shape) != (size,) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"state[{name!r}] must be a contiguous float32 [{size}] tensor (ops.gaussian_adam_state makes the dict)")
+    status = state.get("status")
+    if not torch.is_tensor(status) or tuple(status.shape) != (1,) or status.dtype != torch.int32:
+        raise ValueError("state['status'] must be an int32 [1] tensor")
+    if not torch.is_tensor(noise) or tuple(noise.shape) != (n, 2, 3) or noise.dtype != torch.float32 or not noise.is_contiguous():
+        raise ValueError(f"noise must be a contiguous float32 [{n},2,3] tensor")
+    if not isinstance(out, dict) or any(k not in out for k in FIT_GROUPS + ("m", "v")):
+        raise ValueError("out must be the dict of ops.densify_buffers")
+    n_cap = int(out["xyz"].shape[0])
+    for k in FIT_GROUPS:
+        t = out[k]
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (n_cap, *params[k].shape[1:]):
+            raise ValueError(f"out[{k!r}] must be a contiguous float32 tensor of {n_cap} rows in the shape of params[{k!r}]")
+    for k in ("m", "v"):
+        t = out[k]
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n_cap * (11 + 3 * n_coef):
+            raise ValueError(f"out[{k!r}] must be a contiguous float32 tensor of at least {n_cap * (11 + 3 * n_coef)} entries")
+    _need_gpu(*[params[k] for k in FIT_GROUPS], state["m"], state["v"], status, *[stats[k] for k, _ in DENSIFY_STATS], noise,
+              *[out[k] for k in FIT_GROUPS + ("m", "v")], workspace)
+    lib = _lib.load()
+    dev = params["xyz"].device
+    ws, ws_bytes = _workspace(workspace, lib.sixdgs_densify_workspace_bytes(n), dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    some = lambda t: _p(t if t.numel() else None)
+    check(lib.sixdgs_densify(n, n_coef, *[some(params[k]) for k in FIT_GROUPS], int(bool(scale_is_log)), int(bool(opacity_is_logit)),
+                             some(state["m"]), some(state["v"]), some(stats["grad_accum"]), some(stats["denom"]), some(stats["max_radii"]),
+                             some(noise), float(grad_threshold), float(percent_dense), float(extent), float(min_opacity), int(bool(prune_big)),
+                             int(screen_size), n_cap, *[some(out[k]) for k in FIT_GROUPS], some(out["m"]), some(out["v"]), _p(counts),
+                             _p(status), _p(ws), ws_bytes, _stream()),
+          "densify")
+    return counts
+
+
+def densify(params: dict, state: dict, stats: dict, noise: torch.Tensor, *, grad_threshold: float, percent_dense: float, extent: float,
+            min_opacity: float, prune_big: bool, screen_size: int = 0, scale_is_log: bool = True, opacity_is_logit: bool = True):
+    """One densification round (densify_raw into buffers of 2 n rows, which always fit) -> (new params, new state, counts): dicts like
+    the inputs at n_out rows -- views of the buffers --, the status tensor carried over, counts int64 [4] on the device.  One 8-byte
+    host read: n_out."""
+    n, n_coef = _fit_params(params)
+    out = densify_buffers(params, 2 * n)
+    counts = densify_raw(params, state, stats, noise, out, grad_threshold=grad_threshold, percent_dense=percent_dense, extent=extent,
+                         min_opacity=min_opacity, prune_big=prune_big, screen_size=screen_size, scale_is_log=scale_is_log,
+                         opacity_is_logit=opacity_is_logit)
+    n_out = int(counts[0].item())
+    size = n_out * (11 + 3 * n_coef)
+    return ({k: out[k][:n_out] for k in FIT_GROUPS}, {"m": out["m"][:size], "v": out["v"][:size], "status": state["status"]}, counts)
+
+
+def fit_scene_steps_workspace_bytes(n: int, n_coef: int, batch: int, width: int, height: int, max_instances: int) -> int:
+    return int(_lib.load().sixdgs_fit_scene_steps_workspace_bytes(int(n), int(n_coef), int(batch), int(width), int(height), int(max_instances)))
+
+
+@_on_device
+def fit_scene_steps_raw(params: dict, cams: torch.Tensor, width: int, height: int, target: torch.Tensor, state: dict, *, views, lrs, sh_degrees,
+                        resets=None, updates=None, stats_steps=None, stats: Optional[dict] = None, first_adam_step: int = 0,
+                        groups=FIT_GROUPS, lambda_dssim: float = 0.2, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-15,
+                        reset_ceiling: float = 0.01, scale_modifier: float = 1.0, background=(1.0, 1.0, 1.0), scale_is_log: bool = True,
+                        opacity_is_logit: bool = True, max_instances: Optional[int] = None,
+                        workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A segment of a fit as ONE library call with caller-kept state (sixdgs_fit_scene_steps in include/sixdgs.h): fit_scene_raw's
+    loop on `params` IN PLACE, from and into `state` -- m, v, status (gaussian_adam_state's dict) and instances_needed (int64 [1]) --
+    which the call does not zero and never reads back.  updates [steps] (None: all): a cleared flag makes no Adam update at that step,
+    and Adam's counter, which starts at first_adam_step, does not advance.  stats_steps [steps] (None: none): a set flag accumulates
+    the densification statistics of that step's pass into `stats` (densify_stats_state's dict).  Returns history [steps,batch]; the
+    caller reads state["status"] when it wants to know about the capacity (bit 1) -- nothing is retried here."""
+    (n, n_coef, lam, groups, cams, width, height, n_views, steps, batch, view_t, lr_t, deg_t, reset_t, target, target_is_u8,
+     target_stride) = _fit_args(params, cams, width, height, target, views, lrs, sh_degrees, resets, groups, lambda_dssim, beta1, beta2, eps,
+                                reset_ceiling, scale_modifier, background, opacity_is_logit)
+    flags = []
+    for name, f in (("updates", updates), ("stats_steps", stats_steps)):
+        t = None if f is None else torch.as_tensor(f).detach().cpu().to(torch.bool).to(torch.uint8).contiguous()
+        if t is not None and tuple(t.shape) != (steps,):
+            raise ValueError(f"{name} must be [{steps}] flags")
+        flags.append(t)
+    update_t, stats_t = flags
+    if isinstance(first_adam_step, bool) or int(first_adam_step) != first_adam_step or int(first_adam_step) < 0:
+        raise ValueError(f"first_adam_step must be a non-negative integer (got {first_adam_step})")
+    wants_stats = stats_t is not None and bool(stats_t.any())
+    if wants_stats or stats is not None:
+        _check_stats(stats, n)
+    size = n * (11 + 3 * n_coef)
+    for name, shape, dt in (("m", (size,), torch.float32), ("v", (size,), torch.float32), ("status", (1,), torch.int32),
+                            ("instances_needed", (1,), torch.int64)):
+        t = state.get(name) if isinstance(state, dict) else None
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"state[{name!r}] must be a contiguous {dt} {list(shape)} tensor")
+    capacity = _capacity(max_instances, n, batch)
+    arrays = [params[k] for k in SCENE_ARRAYS]
+    st = [stats[k] for k, _ in DENSIFY_STATS] if stats is not None else [None] * 3
+    _need_gpu(*arrays, cams, target, state["m"], state["v"], state["status"], state["instances_needed"], *st, workspace)
+    lib = _lib.load()
+    dev = cams.device
+    bg = _background(background, dev)
+    history = torch.empty(steps, batch, device=dev)
+    mask = sum(1 << FIT_GROUPS.index(k) for k in groups)
+    need = lib.sixdgs_fit_scene_steps_workspace_bytes(n, n_coef, batch, width, height, capacity)
+    if need == 0:
+        raise ValueError(f"sizes outside the rasteriser's limits (n {n}, batch {batch}, {width} x {height}, instances {capacity})")
+    ws, ws_bytes = _workspace(workspace, need, dev)
+    some = lambda t: _p(t if t is not None and t.numel() else None)
+    check(lib.sixdgs_fit_scene_steps(*_scene_args(arrays, n_coef, scale_is_log, opacity_is_logit), n_coef, n, _p(cams), n_views, width, height,
+                                     float(scale_modifier), _p(bg), _p(target), target_is_u8, target_stride, lam, steps, batch, _p(view_t),
+                                     _p(lr_t), _p(deg_t), _p(reset_t), _p(update_t), _p(stats_t), int(first_adam_step), mask, float(beta1),
+                                     float(beta2), float(eps), float(reset_ceiling), capacity, some(state["m"]), some(state["v"]), _p(history),
+                                     _p(state["status"]), _p(state["instances_needed"]), *[some(t) for t in st], _p(ws), ws_bytes, _stream()),
+          "fit_scene_steps")
+    return history
 
 
 # ---------------------------------------------------------------------------------------------

@@ -415,9 +415,9 @@ int sixdgs_refine_poses(const float* xyz, const float* scale, int scale_is_log, 
                         size_t ws_bytes, sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Adam over a scene's Gaussians and the opacity reset (additive in ABI 10): the optimiser's side of fitting a FIXED set of Gaussians
- * to posed views (the reference's train.py:94-122 and scene/gaussian_model.py:230-282 without densification: n never changes, no
- * clone, split or prune, and none of their statistics).  All arithmetic in fp32, no contraction into fused multiply-adds; one owner
+ * Adam over a scene's Gaussians and the opacity reset (additive in ABI 10): the optimiser's side of fitting a set of Gaussians to
+ * posed views (the reference's train.py:94-122 and scene/gaussian_model.py:230-282; n is fixed within a call -- the densification
+ * round that changes it is sixdgs_densify, further down).  All arithmetic in fp32, no contraction into fused multiply-adds; one owner
  * per output, no floating-point atomics, the same bytes on every call.
  *
  * GROUPS.  Six, in this order everywhere: xyz [n,3], f_dc [n,1,3], f_rest [n,n_coef-1,3], opacity [n], scale [n,3], rot [n,4]:
@@ -460,7 +460,8 @@ int sixdgs_opacity_reset(float* opacity /*[n]*/, int64_t n, int opacity_is_logit
 
 /* ---------------------------------------------------------------------------------------------
  * Fitting a scene's Gaussians to posed views as one call (additive in ABI 10).  The scene arrays are MUTABLE and updated in place; n is
- * fixed for the whole fit (no densification).  The call first zeroes m, v, status[0] and instances_needed[0], then for
+ * fixed for the whole call (a fit that densifies is cut into sixdgs_fit_scene_steps calls around sixdgs_densify).  The call first
+ * zeroes m, v, status[0] and instances_needed[0], then for
  * s = 0 .. steps - 1 enqueues on `stream`, in this order and through the entry points above as they are:
  *   1. the step's views h_view[s][0 .. batch): with batch == 1 pointer offsets into cams and the target, no copy; otherwise
  *      device-to-device copies of the batch's camera rows and target views into the workspace, in slot order (duplicates allowed);
@@ -498,6 +499,89 @@ int sixdgs_fit_scene(float* xyz, float* scale, int scale_is_log, float* rot, flo
                      const int32_t* h_sh_degree /*[steps] host*/, const uint8_t* h_reset /*[steps] host*/, int group_mask, float beta1,
                      float beta2, float eps, float reset_ceiling, int64_t max_instances, float* m, float* v, float* history /*[steps][batch]*/,
                      int32_t* status /*[1]*/, int64_t* instances_needed /*[1]*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Adaptive density control (additive in ABI 10): the statistics the reference gathers per iteration (train.py:152-160,
+ * scene/gaussian_model.py:628-632), one round of its densify_and_prune (gaussian_model.py:539-624) and the fit's loop body with
+ * caller-kept state, so that a fit can run with a changing n.  All arithmetic in fp32, no contraction into fused multiply-adds; one
+ * owner per output, no floating-point atomics, the same bytes on every call.
+ *
+ * sixdgs_densify_stats reads the workspace of a completed sixdgs_raster_views (fwd_ws), the workspace of a completed
+ * sixdgs_raster_views_backward on the same arguments that wrote at least one output (bwd_ws), neither written since, and the forward's
+ * radii [views][n]; it writes nothing to the workspaces.  One lane per Gaussian i, views v in ascending order.  A (v, i) whose tile
+ * rectangle is not empty -- exactly when radii[v][i] > 0, the reference's visibility_filter -- contributes:
+ *   1. du, dv = the sums of entries 0 and 1 of its instance slots, from 0.f in slot order: the bits the backward chained to the
+ *      parameters (dL / d of the centre's pixel coordinates u, v);
+ *   2. a = (0.5f width) du, b = (0.5f height) dv, g = sqrtf(a a + b b): the norm of the gradient by the NDC position, which the
+ *      reference's threshold 0.0002 is tuned to (the upstream rasteriser scales its pixel gradient by 0.5 W, 0.5 H; that submodule is
+ *      not part of the reference tree, so THIS is the definition);
+ *   3. grad_accum[i] += g;  denom[i] += 1 (int32);  max_radii[i] = max(max_radii[i], radii[v][i]).
+ * A Gaussian that covers tiles but blends into no pixel counts as visible with g = 0, as in the reference.  grad2d [views][n][2] (may
+ * be NULL) receives the raw (du, dv): written, not accumulated, exact zeros where the rectangle is empty.  If the recorded instance
+ * total exceeds max_instances, or status (int32 [1] device, may be NULL) has bit 1 set, the kernel changes nothing (grad2d included).
+ * SIXDGS_E_BADARG / SIXDGS_E_WORKSPACE for argument and workspace errors (the rasteriser's size limits; a NULL or misaligned array;
+ * a workspace smaller than sixdgs_raster_views_workspace_bytes / _backward_workspace_bytes say) without touching a GPU; views == 0
+ * or n == 0 returns 0.
+ *
+ * sixdgs_densify is ONE ROUND, out of place: from the six arrays (group order of sixdgs_gaussian_adam), m, v at n, the three
+ * statistics and noise [n][2][3] -- standard normals SUPPLIED BY THE CALLER, so the library holds no random-number generator -- into
+ * the six arrays and m_out, v_out at n_out rows, in caller buffers of n_cap rows (n_cap (11 + 3 n_coef) floats for m_out, v_out, laid out
+ * group after group for n_out rows: the kernels read n_out on the device to place the slices).
+ * THRESHOLDS.  The host converts each once, in double, into the domain the array is stored in, and rounds to float:
+ *   t_dense from (double) percent_dense * (double) extent, t_world from 0.1 * (double) extent: log() of it when scale_is_log;
+ *   t_opacity from p = min_opacity: log(p / (1 - p)) when opacity_is_logit (-inf for p = 0).
+ * All comparisons are on STORED values, so classification uses no transcendental.
+ * RULES, per Gaussian i:  avg = denom > 0 ? grad_accum / (float) denom : 0;  smax = max_k scale_k (fmaxf);  big = smax > t_dense;
+ *   clone = avg >= grad_threshold && !big;  split = avg >= grad_threshold && big.  grad_threshold > 0 is required, so that, as in the
+ *   reference (whose split pass sees a zero gradient for the clones just made), a fresh clone is never split.
+ * CANDIDATES, in the reference's order: originals that are not split, ascending i; clones, ascending source (exact copies);
+ *   children copy 0 of the split sources, ascending source; children copy 1.
+ * CHILD of source i, copy j:  xyz + R (sigma * z), R = the rotation matrix of rot_i (normalised twice, as the rasteriser does),
+ *   sigma_k = expf(scale_k) (the stored value when not log), z = noise[i][j], out_r = xyz_r + ((R_r0 y_0 + R_r1 y_1) + R_r2 y_2) with
+ *   y_k = sigma_k z_k;  scale - 0.470003629f (= logf(1.6), the reference's / (0.8 * 2)) when log, scale / 1.6f otherwise;
+ *   everything else copied from the source.
+ * PRUNE.  Every candidate is tested on its own stored values: opacity < t_opacity; when prune_big != 0 also max_k scale > t_world;
+ *   when prune_big != 0 and screen_size > 0 also max_radii[i] > screen_size, for originals only (clones and children count as 0).
+ *   DEVIATION: the reference zeroes max_radii2D in densification_postfix before it prunes (gaussian_model.py:537, :619), so its
+ *   screen-size test never fires; screen_size = 0 is the reference's behaviour.
+ * COMPACTION.  Survivors are compacted in candidate order (rocPRIM exclusive scan of integer flags).  A surviving original keeps its
+ *   rows of m and v; clones and children get zeros.
+ * counts [4] (int64, device) = n_out, clones, split sources, candidates pruned (n + clones + splits - n_out).  If n_out > n_cap,
+ * nothing is written except counts and bit 1 of status[0] (integer atomic OR; status is not read); n_cap >= 2 n always fits.
+ * Limits: those of sixdgs_gaussian_adam; 0 <= n_cap < 2^31; grad_threshold, percent_dense, extent > 0 finite; 0 <= min_opacity < 1;
+ * screen_size >= 0.  SIXDGS_E_BADARG (a NULL or misaligned array, an output that is its input, m_out == v_out) and
+ * SIXDGS_E_WORKSPACE without touching a GPU; n == 0 writes counts = 0.  sixdgs_densify_workspace_bytes is answered without a GPU
+ * (0 outside n < 2^31): two uint32 arrays of 4 n + 1 and the scan's temporary storage, reserved by bound.
+ *
+ * sixdgs_fit_scene_steps is the loop body of sixdgs_fit_scene with caller-kept state: it does NOT zero m, v, status[0] or
+ * instances_needed[0].  Per step s as sixdgs_fit_scene's 1 - 7, with:
+ *   - h_stats[s] != 0 (host [steps], NULL = never): behind 5, sixdgs_densify_stats on the step's workspaces and radii (kept in this
+ *     call's workspace) into grad_accum, denom, max_radii, with status -- statistics are not accumulated once bit 1 is set;
+ *   - h_update[s] == 0 (host [steps], NULL = every step updates): step s makes no Adam update and Adam's counter does not advance;
+ *     the u-th update of the call is sixdgs_gaussian_adam's step first_adam_step + u.
+ * sixdgs_fit_scene is the zeroing followed by this function with all updates on, no statistics and first_adam_step = 0.
+ * sixdgs_fit_scene_steps_workspace_bytes = sixdgs_fit_scene_workspace_bytes plus the radii [batch][n] int32 (0 outside the limits). */
+int sixdgs_densify_stats(int64_t n, int views, int width, int height, int64_t max_instances, const void* fwd_ws, size_t fwd_ws_bytes,
+                         const void* bwd_ws, size_t bwd_ws_bytes, const int32_t* radii /*[views][n]*/, float* grad_accum /*[n]*/,
+                         int32_t* denom /*[n]*/, int32_t* max_radii /*[n]*/, float* grad2d /*[views][n][2] or NULL*/,
+                         const int32_t* status /*[1] device or NULL*/, sixdgs_stream_t stream);
+size_t sixdgs_densify_workspace_bytes(int64_t n);
+int sixdgs_densify(int64_t n, int n_coef, const float* xyz, const float* f_dc, const float* f_rest, const float* opacity, const float* scale,
+                   const float* rot, int scale_is_log, int opacity_is_logit, const float* m, const float* v, const float* grad_accum /*[n]*/,
+                   const int32_t* denom /*[n]*/, const int32_t* max_radii /*[n]*/, const float* noise /*[n][2][3]*/, float grad_threshold,
+                   float percent_dense, float extent, float min_opacity, int prune_big, int screen_size, int64_t n_cap, float* xyz_out,
+                   float* f_dc_out, float* f_rest_out, float* opacity_out, float* scale_out, float* rot_out, float* m_out, float* v_out,
+                   int64_t* counts /*[4] device*/, int32_t* status /*[1] device*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
+size_t sixdgs_fit_scene_steps_workspace_bytes(int64_t n, int n_coef, int batch, int width, int height, int64_t max_instances);
+int sixdgs_fit_scene_steps(float* xyz, float* scale, int scale_is_log, float* rot, float* opacity, int opacity_is_logit, float* f_dc,
+                           float* f_rest, int n_coef, int64_t n, const float* cams /*[views][16]*/, int views, int width, int height,
+                           float scale_modifier, const float* background /*[3] device*/, const void* target, int target_is_u8,
+                           int target_stride, float lambda, int steps, int batch, const int32_t* h_view, const float* h_lr,
+                           const int32_t* h_sh_degree, const uint8_t* h_reset, const uint8_t* h_update /*[steps] host or NULL*/,
+                           const uint8_t* h_stats /*[steps] host or NULL*/, int first_adam_step, int group_mask, float beta1, float beta2,
+                           float eps, float reset_ceiling, int64_t max_instances, float* m, float* v, float* history, int32_t* status,
+                           int64_t* instances_needed, float* grad_accum, int32_t* denom, int32_t* max_radii, void* ws, size_t ws_bytes,
+                           sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Scorer, scene side (once per scene): ray MLP + k_proj -> key cache

@@ -1,13 +1,18 @@
 """Fit a perturbed stand-in scene back to views of the scene that rendered them, with both backends of fit.fit_scene.
 
     python tools/fit_standin.py [--gaussians 5000] [--size 112] [--views 8] [--steps 60] [--batch 1] [--rounds 3]
+    python tools/fit_standin.py --densify [--keep 0.5] [--enlarge 1.5] [--from_iter 5] [--until_iter 15] [--interval 10] [--grad 5e-3]
 
 A stand-in scene (synthetic.make_scene) renders `views` views with renderer="raster"; a copy is perturbed -- colours, opacity logits,
 positions and log-scales by Gaussian noise of the given standard deviations -- and fitted to the views.  In one process the two arms
 alternate `rounds` times after one warm-up call each, the arrangement of tools/time_refine.py: backend="torch" (autograd and
 torch.optim.Adam around the kernels) and backend="fused" (one sixdgs_fit_scene call).  HIP events around the whole fit_scene call --
 the target's preparation, the scene's copy and the final read included -- divided by the steps.  Prints ms per step, the loss
-histories' largest difference, and the parameters' RMS distance from the rendering scene before and after; asserts nothing."""
+histories' largest difference, and the parameters' RMS distance from the rendering scene before and after; asserts nothing.
+
+--densify: the stand-in with a share of its Gaussians removed and the rest enlarged (thinned) is fitted back to the views with and
+without densification, on the fused backend and on the torch arm: the rounds, the number of Gaussians and the loss of the first and
+last passes of each."""
 import argparse
 import importlib
 import os
@@ -36,6 +41,31 @@ def perturbed(pkg, scene, sizes, seed):
     return out
 
 
+def thinned(pkg, scene, keep, enlarge, seed):
+    """A random share `keep` of the scene's Gaussians, their scales multiplied by `enlarge`."""
+    n = len(scene)
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:max(int(keep * n), 1)].sort().values.to(scene._xyz.device)
+    out = pkg.GaussianScene(scene.max_sh_degree)
+    for k, a in ATTR.items():
+        setattr(out, a, getattr(scene, a)[idx].clone() + (float(np.log(enlarge)) if k == "scale" else 0.0))
+    return out
+
+
+def densify_demo(pkg, fit, scene, images, c2w, K, args):
+    thin = thinned(pkg, scene, args.keep, args.enlarge, args.seed)
+    opts = dict(from_iter=args.from_iter, until_iter=args.until_iter, interval=args.interval, grad_threshold=args.grad)
+    print(f"{len(scene)} Gaussians thinned to {len(thin)} (scales x {args.enlarge}), {args.views} views of {args.size} x {args.size}, {args.steps} steps; "
+          f"densify {opts}, extent {fit.cameras_extent(c2w):.3f}")
+    tail = max(min(args.views // args.batch, args.steps), 1)
+    for name, kw in (("fixed n, fused", dict(backend="fused")), ("densify, fused", dict(backend="fused", densify=opts)),
+                     ("densify, torch", dict(backend="torch", densify=opts))):
+        new, rep = fit.fit_scene(thin, images, c2w, K, steps=args.steps, batch=args.batch, **kw)
+        h = rep["loss_history"]
+        rounds = rep["rounds"].tolist() if "rounds" in rep else []
+        print(f"{name}: n {len(thin)} -> {len(new)}; loss, mean of the first {tail} steps {float(h[:tail].mean()):.5f}, of the last {tail} "
+              f"{float(h[-tail:].mean()):.5f}; status {int(rep['status'])}; rounds (iteration, n, clones, splits, pruned, n after): {rounds}")
+
+
 def rms(a, b):
     return {k: float((getattr(a, attr) - getattr(b, attr)).pow(2).mean().sqrt()) for k, attr in ATTR.items()}
 
@@ -53,6 +83,13 @@ def main():
     ap.add_argument("--opacity", type=float, default=0.5, help="noise on the opacity logits")
     ap.add_argument("--position", type=float, default=0.002, help="noise on xyz")
     ap.add_argument("--log_scale", type=float, default=0.05, help="noise on the log-scales")
+    ap.add_argument("--densify", action="store_true", help="fit a thinned copy back, with and without densification")
+    ap.add_argument("--keep", type=float, default=0.5, help="--densify: the share of the Gaussians kept")
+    ap.add_argument("--enlarge", type=float, default=1.5, help="--densify: the factor on the kept Gaussians' scales")
+    ap.add_argument("--from_iter", type=int, default=5)
+    ap.add_argument("--until_iter", type=int, default=15)
+    ap.add_argument("--interval", type=int, default=10)
+    ap.add_argument("--grad", type=float, default=5e-3, help="--densify: grad_threshold")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("fit_standin needs a GPU")
@@ -62,6 +99,8 @@ def main():
     scene, _, held = ts.build_standin(args.gaussians, args.seed, 2, args.views, args.size, renderer="raster")
     c2w, Ks = zip(*[test.gt_pose_and_intrinsics(c, "cpu") for c in held])
     c2w, K, images = torch.stack(c2w), torch.stack(Ks), [c.image for c in held]
+    if args.densify:
+        return densify_demo(pkg, fit, scene, images, c2w, K, args)
     start = perturbed(pkg, scene, {"f_dc": args.colour, "opacity": args.opacity, "xyz": args.position, "scale": args.log_scale}, args.seed)
     print(f"{args.gaussians} Gaussians, {args.views} views of {args.size} x {args.size}, {args.steps} steps of {args.batch}, {args.rounds} rounds")
     ms, out = {"torch": [], "fused": []}, {}
