@@ -74,6 +74,8 @@ SIGNATURES = {
     "sixdgs_densify_stats": (i32, [i64, i32, i32, i32, i64, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
     "sixdgs_densify_workspace_bytes": (sz, [i64]),
     "sixdgs_densify": (i32, [i64, i32] + [vp] * 6 + [i32, i32] + [vp] * 6 + [C.c_float] * 4 + [i32, i32, i64] + [vp] * 8 + [vp, vp, vp, sz, vp]),
+    "sixdgs_knn_workspace_bytes": (sz, [i64]),
+    "sixdgs_knn_mean_dist2": (i32, [i64, vp, vp, vp, sz, vp]),
     "sixdgs_fit_scene_steps_workspace_bytes": (sz, [i64, i32, i32, i32, i32, i64]),
     "sixdgs_fit_scene_steps": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i64, vp, i32, i32, i32, C.c_float, vp, vp, i32, i32, C.c_float, i32, i32,
                                      vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, i64] + [vp] * 5 + [vp] * 3

@@ -1,7 +1,8 @@
 // hostcheck.cpp -- HOST instantiation of device_math.h (the per-thread math of the HIP kernels), of dense_layout.h (the index
 // arithmetic of the ray-MLP chain's operand planes), of pose_step.h (the per-view arithmetic of pose refinement) and of adam_step.h
 // (the per-entry arithmetic of fitting a scene's Gaussians) behind a tiny C ABI, so the CPU test-suite can compare the product's arithmetic with the oracle and the
-// golden vectors without a GPU.  densify_rules.h (the per-entry rules of a densification round) is instantiated here too.  Contains no kernels; never used by the product path.
+// golden vectors without a GPU.  densify_rules.h (the per-entry rules of a densification round) and knn_rules.h (the pair and box rules
+// of the 3-nearest-neighbour search) are instantiated here too.  Contains no kernels; never used by the product path.
 #include <stdlib.h>
 
 #include "device_math.h"
@@ -11,6 +12,10 @@
 #include "pose_step.h"
 #include "adam_step.h"
 #include "densify_rules.h"
+#include "knn_rules.h"
+
+#include <algorithm>
+#include <vector>
 using namespace sdg;
 
 extern "C" {
@@ -249,6 +254,71 @@ void hc_dn_round(long long n, const float* xyz, const float* opacity, const floa
       dn::child_xyz(xyz + 3 * i, rot + 4 * i, scale + 3 * i, scale_is_log != 0, noise + (i * 2 + j) * 3, child_xyz + (i * 2 + j) * 3);
     for (int k = 0; k < 3; ++k) child_scale[3 * i + k] = dn::child_scale(scale[3 * i + k], scale_is_log != 0);
   }
+}
+// ---- knn_rules.h: the pair and box rules of knn.hip (tests/test_knn_host.py) ----
+int hc_knn_box() { return kn::kBox; }
+void hc_knn_morton(long long n, const float* xyz, const float* lo, const float* hi, unsigned* code, unsigned* cells) {
+  for (long long i = 0; i < n; ++i) {
+    code[i] = kn::morton(xyz + 3 * i, lo, hi);
+    for (int a = 0; a < 3; ++a) cells[3 * i + a] = kn::axis_cell(xyz[3 * i + a], lo[a], hi[a]);
+  }
+}
+// per query q[i] and box (lo[i], hi[i]): box_d2; per pair: d2 from q[i] to p[i]
+void hc_knn_box_d2(long long n, const float* q, const float* lo, const float* hi, float* out) {
+  for (long long i = 0; i < n; ++i) out[i] = kn::box_d2(q[3 * i], q[3 * i + 1], q[3 * i + 2], lo + 3 * i, hi + 3 * i);
+}
+void hc_knn_box_box_d2(long long n, const float* qlo, const float* qhi, const float* lo, const float* hi, float* out) {
+  for (long long i = 0; i < n; ++i) out[i] = kn::box_box_d2(qlo + 3 * i, qhi + 3 * i, lo + 3 * i, hi + 3 * i);
+}
+void hc_knn_pair_d2(long long n, const float* q, const float* p, float* out) {
+  for (long long i = 0; i < n; ++i) out[i] = kn::pair_d2(q[3 * i], q[3 * i + 1], q[3 * i + 2], p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+}
+// sixdgs_knn_mean_dist2's whole scheme on the host: bounding box, Morton codes, a stable sort, boxes of `box` consecutive sorted points
+// with their AABBs, and per query the own box, then the others outward, pruned with box_d2 >= best[2] -> mean_d2 [n]; visited (may be
+// NULL) receives the number of boxes walked per query.  Returns 0, or -1 for n < 4.
+int hc_knn_boxed(long long n, const float* xyz, int box, float* mean_d2, int* visited) {
+  if (n < 4 || box < 1) return -1;
+  float lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) lo[a] = INFINITY, hi[a] = -INFINITY;
+  for (long long i = 0; i < n; ++i)
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = fminf(lo[a], xyz[3 * i + a]);
+      hi[a] = fmaxf(hi[a], xyz[3 * i + a]);
+    }
+  std::vector<unsigned> code(n);
+  std::vector<long long> order(n);
+  for (long long i = 0; i < n; ++i) {
+    code[i] = kn::morton(xyz + 3 * i, lo, hi);
+    order[i] = i;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](long long a, long long b) { return code[a] < code[b]; });
+  const long long nb = (n + box - 1) / box;
+  std::vector<float> s(3 * n), blo(3 * nb, INFINITY), bhi(3 * nb, -INFINITY);
+  for (long long k = 0; k < n; ++k)
+    for (int a = 0; a < 3; ++a) {
+      const float c = s[3 * k + a] = xyz[3 * order[k] + a];
+      blo[3 * (k / box) + a] = fminf(blo[3 * (k / box) + a], c);
+      bhi[3 * (k / box) + a] = fmaxf(bhi[3 * (k / box) + a], c);
+    }
+  for (long long k = 0; k < n; ++k) {
+    const float qx = s[3 * k], qy = s[3 * k + 1], qz = s[3 * k + 2];
+    float b0 = INFINITY, b1 = INFINITY, b2 = INFINITY;
+    const long long own = k / box;
+    int walked = 0;
+    for (long long step = 0; step < nb; ++step)
+      for (int side = 0; side < (step ? 2 : 1); ++side) {
+        const long long c = side ? own + step : own - step;
+        if (c < 0 || c >= nb) continue;
+        if (step && kn::box_d2(qx, qy, qz, &blo[3 * c], &bhi[3 * c]) >= b2) continue;
+        ++walked;
+        const long long end = std::min(n, (c + 1) * box);
+        for (long long j = c * box; j < end; ++j)
+          if (j != k) kn::insert3(kn::pair_d2(qx, qy, qz, s[3 * j], s[3 * j + 1], s[3 * j + 2]), b0, b1, b2);
+      }
+    mean_d2[order[k]] = kn::mean3(b0, b1, b2);
+    if (visited) visited[order[k]] = walked;
+  }
+  return 0;
 }
 int hc_dl_const(int which) {
   const int v[] = {dl::kSlabB, dl::kPRow, dl::kGran, dl::kGranSlab, dl::kChunkRun};

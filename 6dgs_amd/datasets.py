@@ -10,7 +10,11 @@ generate_all_possible_rays / test_pose_estimation on a real scene.
 Host-side I/O only (numpy + PIL): every loader returns the reference's `SceneInfo(train_cameras, test_cameras, ...)` of
 `CameraInfo(uid, R, T, FovY, FovX, image, image_path, image_name, width, height)` tuples, R stored transposed (world-to-camera
 rotation transposed, the 3DGS convention), which is exactly what test_pose_estimation consumes.  The sparse point cloud
-(`points3D.*`) is only the 3DGS trainer's initialisation and is not read here; `ply_path` is still reported.
+(`points3D.*`) is the initialisation of a scene that is fitted here (GaussianScene.from_points, fit.fit_scene): the loaders still
+leave `point_cloud` None and report `ply_path`; `read_point_cloud(source_path)` reads it (points3D.ply, else .bin, else .txt).
+
+  point cloud            BasicPointCloud, read_points3D_binary / _text,        utils/graphics_utils.py:18, scene/colmap_utils.py:83-153,
+                         fetch_ply, store_ply, read_point_cloud                scene/datasets_utils.py:32-58, scene/colmap.py:102-117
 
 The `cfg_args` file is the text of an argparse `Namespace(k=v, ...)`.  The reference parses it with an ANTLR grammar
 (cfg_grammar/Namespace.g4: values are INT | FLOAT | BOOL | STRING) and converts booleans with `bool(text)`
@@ -291,6 +295,139 @@ def read_colmap_scene_info(path, images, eval, llffhold: int = 8) -> SceneInfo:
     train = [c for i, c in enumerate(cams) if not eval or i % llffhold != 0]
     test = [c for i, c in enumerate(cams) if eval and i % llffhold == 0]
     return SceneInfo(None, train, test, nerfpp_norm(train), os.path.join(sparse, "points3D.ply"))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The sparse point cloud a scene is started from (GaussianScene.from_points): <path>/sparse/0/points3D.{ply,bin,txt}
+# ---------------------------------------------------------------------------------------------------------------------------
+class BasicPointCloud(NamedTuple):    # utils/graphics_utils.py:18-21
+    points: np.ndarray
+    colors: np.ndarray
+    normals: np.ndarray
+
+
+def read_points3D_binary(path):
+    """points3D.bin (scene/colmap_utils.py:125-153): uint64 count; per point uint64 id, float64 xyz[3], uint8 rgb[3], float64 error,
+    uint64 track length and that many (int32 image id, int32 point2D index) pairs, which are skipped
+    -> xyz float64 [n,3], rgb float64 [n,3] (0..255), error float64 [n,1]."""
+    with open(path, "rb") as f:
+        (n,) = struct.unpack("<Q", f.read(8))
+        xyz, rgb, err = np.empty((n, 3)), np.empty((n, 3)), np.empty((n, 1))
+        for i in range(n):
+            rec = f.read(43)
+            if len(rec) != 43:
+                raise RuntimeError(f"{path}: truncated at point {i} of {n}")
+            v = struct.unpack("<QdddBBBd", rec)
+            xyz[i], rgb[i], err[i] = v[1:4], v[4:7], v[7]
+            (track,) = struct.unpack("<Q", f.read(8))
+            f.seek(8 * track, os.SEEK_CUR)
+    return xyz, rgb, err
+
+
+def read_points3D_text(path):
+    """points3D.txt (scene/colmap_utils.py:83-123): per line `id x y z r g b error track...`; '#' starts a comment."""
+    rows = []
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if line and not line.startswith("#"):
+                e = line.split()
+                rows.append([float(v) for v in e[1:4]] + [float(int(v)) for v in e[4:7]] + [float(e[7])])
+    a = np.array(rows, np.float64).reshape(len(rows), 7)
+    return a[:, 0:3].copy(), a[:, 3:6].copy(), a[:, 6:7].copy()
+
+
+_PLY_TYPES = {"float": "f4", "float32": "f4", "double": "f8", "float64": "f8", "uchar": "u1", "uint8": "u1", "char": "i1", "int8": "i1",
+              "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4"}
+
+
+def store_ply(path, xyz, rgb):
+    """scene/datasets_utils.py:41-58: one `vertex` element of x y z nx ny nz float32 (normals zero) and red green blue uchar, binary
+    little endian (what plyfile writes there)."""
+    xyz, rgb = np.asarray(xyz), np.asarray(rgb)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape:
+        raise ValueError(f"xyz and rgb must both be [n,3] (got {xyz.shape} and {rgb.shape})")
+    v = np.zeros(xyz.shape[0], dtype=[(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")] + [(k, "u1") for k in ("red", "green", "blue")])
+    for a, k in enumerate(("x", "y", "z")):
+        v[k] = xyz[:, a]
+    for a, k in enumerate(("red", "green", "blue")):
+        v[k] = rgb[:, a]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % xyz.shape[0]).encode())
+        f.write("".join(f"property float {k}\n" for k in ("x", "y", "z", "nx", "ny", "nz")).encode())
+        f.write("".join(f"property uchar {k}\n" for k in ("red", "green", "blue")).encode())
+        f.write(b"end_header\n")
+        f.write(v.tobytes())
+
+
+def fetch_ply(path) -> BasicPointCloud:
+    """scene/datasets_utils.py:32-38 without plyfile: the `vertex` element's x y z, red green blue / 255 and nx ny nz (zeros when the file
+    has none).  Binary of either byte order or ascii; any property order and scalar type; further elements are ignored."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise RuntimeError(f"{path}: not a PLY file")
+        fmt, n, props, in_vertex, before = None, None, [], False, True
+        while True:
+            line = f.readline()
+            if not line:
+                raise RuntimeError(f"{path}: truncated PLY header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] == "comment":
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                in_vertex = tok[1] == "vertex" and n is None
+                if in_vertex:
+                    n = int(tok[2])
+                elif n is None:
+                    before = False              # an element in front of the vertices: its size is not known without parsing it
+            elif tok[0] == "property" and in_vertex:
+                if tok[1] == "list":
+                    raise RuntimeError(f"{path}: list property in the vertex element")
+                props.append((tok[2], _PLY_TYPES[tok[1]]))
+            elif tok[0] == "end_header":
+                break
+        if n is None or not before:
+            raise RuntimeError(f"{path}: need a PLY whose first element is `vertex`")
+        if fmt == "ascii":
+            rows = [f.readline().split() for _ in range(n)]
+            if any(len(r) != len(props) for r in rows):
+                raise RuntimeError(f"{path}: a vertex line does not hold {len(props)} values")
+            data = {nm: np.array([r[k] for r in rows], dtype=np.float64) for k, (nm, _) in enumerate(props)}
+        elif fmt in ("binary_little_endian", "binary_big_endian"):
+            end = "<" if fmt == "binary_little_endian" else ">"
+            rec = np.fromfile(f, dtype=np.dtype([(nm, end + t) for nm, t in props]), count=n)
+            if rec.shape[0] != n:
+                raise RuntimeError(f"{path}: {rec.shape[0]} of {n} vertices present")
+            data = {nm: rec[nm] for nm, _ in props}
+        else:
+            raise RuntimeError(f"{path}: unknown PLY format {fmt}")
+    for k in ("x", "y", "z", "red", "green", "blue"):
+        if k not in data:
+            raise RuntimeError(f"{path}: the vertex element has no property {k}")
+
+    def cols(names):
+        return np.vstack([data[k] for k in names]).T
+
+    normals = cols(("nx", "ny", "nz")) if all(k in data for k in ("nx", "ny", "nz")) else np.zeros((n, 3), np.float32)
+    return BasicPointCloud(points=cols(("x", "y", "z")), colors=cols(("red", "green", "blue")) / 255.0, normals=normals)
+
+
+def read_point_cloud(source_path) -> BasicPointCloud:
+    """The point cloud of a COLMAP scene in the reference's order (scene/colmap.py:102-117): sparse/0/points3D.ply if it exists, else
+    points3D.bin, else points3D.txt; colours in [0,1].  Unlike the reference, which converts .bin / .txt to a .ply beside them on first
+    use, nothing is written here: the dataset is only read (store_ply does that conversion when asked)."""
+    sparse = os.path.join(source_path, "sparse/0")
+    ply = os.path.join(sparse, "points3D.ply")
+    if os.path.exists(ply):
+        return fetch_ply(ply)
+    try:
+        xyz, rgb, _ = read_points3D_binary(os.path.join(sparse, "points3D.bin"))
+    except Exception:
+        xyz, rgb, _ = read_points3D_text(os.path.join(sparse, "points3D.txt"))
+    return BasicPointCloud(points=xyz, colors=rgb / 255.0, normals=np.zeros_like(xyz))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

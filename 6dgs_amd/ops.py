@@ -1087,6 +1087,32 @@ def densify(params: dict, state: dict, stats: dict, noise: torch.Tensor, *, grad
     return ({k: out[k][:n_out] for k in FIT_GROUPS}, {"m": out["m"][:size], "v": out["v"][:size], "status": state["status"]}, counts)
 
 
+def knn_workspace_bytes(n: int) -> int:
+    return int(_lib.load().sixdgs_knn_workspace_bytes(int(n)))
+
+
+@_on_device
+def knn_mean_dist2(xyz: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mean squared distance of every point to its three nearest OTHER points (sixdgs_knn_mean_dist2 in include/sixdgs.h: exact, the
+    bits of an fp32 brute force; the reference's distCUDA2) -> float32 [n].  xyz: contiguous float32 [n,3] on the GPU, finite, n == 0
+    or n >= 4.  One stream-ordered call, no host read."""
+    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != torch.float32 or not xyz.is_contiguous():
+        raise ValueError("xyz must be a contiguous float32 [n,3] tensor")
+    n = int(xyz.shape[0])
+    if 1 <= n <= 3:
+        raise ValueError(f"knn_mean_dist2 needs at least 4 points: every point has three neighbours (got {n})")
+    if workspace is not None and (not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or not workspace.is_contiguous()):
+        raise ValueError("workspace must be a contiguous uint8 tensor")
+    _need_gpu(xyz, workspace)
+    out = torch.empty(n, dtype=torch.float32, device=xyz.device)
+    if n == 0:
+        return out
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(workspace, lib.sixdgs_knn_workspace_bytes(n), xyz.device)
+    check(lib.sixdgs_knn_mean_dist2(n, _p(xyz.detach()), _p(out), _p(ws), ws_bytes, _stream()), "knn_mean_dist2")
+    return out
+
+
 def fit_scene_steps_workspace_bytes(n: int, n_coef: int, batch: int, width: int, height: int, max_instances: int) -> int:
     return int(_lib.load().sixdgs_fit_scene_steps_workspace_bytes(int(n), int(n_coef), int(batch), int(width), int(height), int(max_instances)))
 

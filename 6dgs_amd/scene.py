@@ -64,6 +64,66 @@ class GaussianScene:
         return cls.from_arrays(d["xyz"], d["log_scale"], d["rot"], d["f_dc"], d["f_rest"], d.get("opacity"),
                                int(d["sh_degree"]) if "sh_degree" in d else None, device)
 
+    # ---- from a point cloud (gaussian_model.py:189-228) ---------------------------------------------------------------
+    @classmethod
+    def from_points(cls, points, colors, sh_degree: int = 3, *, opacity: float = 0.1, min_dist2: float = 1e-7, mean_dist2=None,
+                    device="cuda"):
+        """GaussianModel.create_from_pcd's arithmetic: positions from `points` [n,3], SH DC (rgb - 0.5) / C0 from `colors` [n,3] in [0,1],
+        zero higher SH, the identity rotation, opacity logit(opacity) and an isotropic scale log(sqrt(max(d2, min_dist2))), d2 the mean
+        squared distance to the three nearest other points: `mean_dist2` [n] when given, else ops.knn_mean_dist2 on the device (a HIP
+        kernel; there is no CPU search).  active_sh_degree is 0, as the reference's constructor leaves it."""
+        def t(a, what):
+            a = torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a)
+            if not (a.is_floating_point() or a.dtype in (torch.uint8, torch.int16, torch.int32, torch.int64)):
+                raise ValueError(f"{what} must be numeric (got {a.dtype})")
+            return a.detach().to(torch.float32)
+
+        xyz, rgb = t(points, "points"), t(colors, "colors")
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or tuple(rgb.shape) != tuple(xyz.shape):
+            raise ValueError(f"points and colors must both be [n,3] (got {tuple(xyz.shape)} and {tuple(rgb.shape)})")
+        n = xyz.shape[0]
+        if n < 4:
+            raise ValueError(f"a scene from points needs at least 4 points: every point has three neighbours (got {n})")
+        if not bool(torch.isfinite(xyz).all()):
+            raise ValueError("points must be finite")
+        if isinstance(sh_degree, bool) or int(sh_degree) != sh_degree or not 0 <= int(sh_degree) <= 3:
+            raise ValueError(f"sh_degree must be 0..3 (got {sh_degree})")
+        if not 0.0 < float(opacity) < 1.0:
+            raise ValueError(f"opacity must lie in (0, 1) (got {opacity})")
+        if not float(min_dist2) > 0.0:
+            raise ValueError(f"min_dist2 must be positive (got {min_dist2})")
+        # colours and the opacity logit are computed on the host, so that their bits do not depend on how a device divides
+        f_dc = ((rgb.cpu() - 0.5) / 0.28209479177387814)[:, None, :].contiguous()
+        p = opacity * torch.ones(n, 1, dtype=torch.float32)
+        logit = torch.log(p / (1 - p))
+        xyz = xyz.to(device).contiguous()
+        if mean_dist2 is None:
+            from . import ops
+            d2 = ops.knn_mean_dist2(xyz)
+        else:
+            d2 = t(mean_dist2, "mean_dist2").to(device)
+            if tuple(d2.shape) != (n,):
+                raise ValueError(f"mean_dist2 must be [{n}] (got {tuple(d2.shape)})")
+        s = cls(int(sh_degree))
+        s.active_sh_degree = 0
+        s._xyz = xyz
+        s._features_dc = f_dc.to(xyz.device)
+        s._features_rest = torch.zeros(n, (int(sh_degree) + 1) ** 2 - 1, 3, device=xyz.device)
+        s._scaling = torch.log(torch.sqrt(torch.clamp_min(d2, float(min_dist2))))[:, None].repeat(1, 3)
+        s._rotation = torch.zeros(n, 4, device=xyz.device)
+        s._rotation[:, 0] = 1
+        s._opacity = logit.to(xyz.device)
+        return s
+
+    def create_from_pcd(self, pcd, spatial_lr_scale: float, device="cuda"):
+        """The reference's name for it, on an instance: fills this scene from pcd.points / pcd.colors (a datasets.BasicPointCloud) at this
+        scene's max_sh_degree and keeps spatial_lr_scale."""
+        o = type(self).from_points(np.asarray(pcd.points), np.asarray(pcd.colors), self.max_sh_degree, device=device)
+        for k in ("_xyz", "_scaling", "_rotation", "_features_dc", "_features_rest", "_opacity", "active_sh_degree"):
+            setattr(self, k, getattr(o, k))
+        self.spatial_lr_scale = spatial_lr_scale
+        return self
+
     # ---- 3DGS PLY (gaussian_model.py:284-340 writes it, :342-420 reads it) --------------------------
     # One "vertex" element of float32 properties x y z nx ny nz f_dc_0..2 f_rest_0..(3*((deg+1)^2-1)-1) opacity scale_0..2
     # rot_0..3, binary little endian.  f_dc / f_rest are stored channel-major ([N,3,coeffs] flattened) and transposed to

@@ -584,6 +584,39 @@ int sixdgs_fit_scene_steps(float* xyz, float* scale, int scale_is_log, float* ro
                            sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Starting a scene from a point cloud (additive in ABI 10): the mean squared distance of every point to its three nearest other
+ * points, from which GaussianModel.create_from_pcd (scene/gaussian_model.py:189-228) takes the isotropic start scale
+ * log(sqrt(max(d2, 1e-7))); the reference's distCUDA2 (submodules/simple-knn).  An EXACT search, not an approximate one.
+ * PAIR DISTANCE.  For points i != j -- distinct by index, not by position --
+ *   d2(i, j) = (dx dx + dy dy) + dz dz in fp32, dx = x_j - x_i, dy = y_j - y_i, dz = z_j - z_i; no contraction into fused multiply-adds.
+ * RESULT.  b0 <= b1 <= b2 the three smallest values of the multiset { d2(i, j) : j != i }:  mean_d2[i] = ((b0 + b1) + b2) / 3.0f.
+ *   Exact duplicates of a point therefore contribute zeros.
+ * BIT DETERMINISM.  Every d2(i, j) is one fixed fp32 number and the three smallest values of a multiset do not depend on the order it
+ *   is searched in, so the result is determined to the bit whatever the search structure: it is what a brute force over all pairs
+ *   in fp32 gives, and that is the acceptance criterion.
+ * SEARCH (informative; csrc/knn.hip, rules in csrc/knn_rules.h).  The points are sorted by a 30-bit Morton code inside their bounding
+ *   box -- per axis cell = hi > lo ? clamp((int)((c - lo) / (hi - lo) * 1023.0f), 0, 1023) : 0 -- and cut into boxes of 256 consecutive
+ *   sorted points with their AABBs.  The distance from a query to a box, per axis q < lo ? lo - q : (q > hi ? q - hi : 0), summed in
+ *   d2's order, is a lower bound of d2 to every point of the box in fp32 itself (every operation in it is monotone), so a box with
+ *   box_d2 >= b2 is skipped without changing the result: a candidate that can only tie the third-best value changes none of the
+ *   three.  A cloud of identical points is therefore searched in linear time.
+ * DEVIATIONS from the reference, stated: its CUDA build may contract the sum into fused multiply-adds (last-ulp differences), and it
+ *   divides by a zero extent when an axis of the cloud is flat; this call does neither.  With fewer than four points the reference
+ *   returns inf; this call refuses them.
+ * LIMITS.  n == 0 returns 0.  1 <= n <= 3 (fewer than three neighbours), n >= 2^31, a NULL or misaligned pointer (xyz, mean_d2: 4 bytes;
+ *   ws: 256), mean_d2 overlapping xyz: SIXDGS_E_BADARG.  ws_bytes < sixdgs_knn_workspace_bytes(n): SIXDGS_E_WORKSPACE.  All answered
+ *   without touching a GPU, as is sixdgs_knn_workspace_bytes (0 for n < 4 and n >= 2^31): the bounding-box partials, two (code, index)
+ *   buffers of n uint32 pairs, the sort's temporary storage reserved by bound, three planes of the sorted points padded to whole boxes
+ *   and the box table.
+ * PRECONDITION.  Coordinates are finite with |c| < 2^62, so that d2 is finite.  Nothing derived from a coordinate is ever used as an
+ *   index (Morton codes are sort keys only, cells are clamped) and every loop is bounded by n or the box count: a violated
+ *   precondition gives meaningless numbers, not a fault or a hang.
+ * EXECUTION.  Stream-ordered, no host read-back (the bounding box stays on the device), one owner per output, no atomics: the same
+ *   bytes on every call. */
+size_t sixdgs_knn_workspace_bytes(int64_t n);
+int sixdgs_knn_mean_dist2(int64_t n, const float* xyz /*[n][3]*/, float* mean_d2 /*[n]*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scorer, scene side (once per scene): ray MLP + k_proj -> key cache
  * replaces RayPreprocessor.forward (ray_preprocessor.py:36-46) + k_proj (our_multihead_attention.py:74)
  * ------------------------------------------------------------------------------------------- */

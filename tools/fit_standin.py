@@ -2,6 +2,7 @@
 
     python tools/fit_standin.py [--gaussians 5000] [--size 112] [--views 8] [--steps 60] [--batch 1] [--rounds 3]
     python tools/fit_standin.py --densify [--keep 0.5] [--enlarge 1.5] [--from_iter 5] [--until_iter 15] [--interval 10] [--grad 5e-3]
+    python tools/fit_standin.py --from-points 2000 [--from_iter 5] [--until_iter 15] [--interval 10] [--grad 5e-3]
 
 A stand-in scene (synthetic.make_scene) renders `views` views with renderer="raster"; a copy is perturbed -- colours, opacity logits,
 positions and log-scales by Gaussian noise of the given standard deviations -- and fitted to the views.  In one process the two arms
@@ -12,7 +13,11 @@ histories' largest difference, and the parameters' RMS distance from the renderi
 
 --densify: the stand-in with a share of its Gaussians removed and the rest enlarged (thinned) is fitted back to the views with and
 without densification, on the fused backend and on the torch arm: the rounds, the number of Gaussians and the loss of the first and
-last passes of each."""
+last passes of each.
+
+--from-points N: N of the stand-in's centres with their DC colours, as a sparse point cloud would give them, become a scene through
+GaussianScene.from_points (isotropic scales from the 3-nearest-neighbour kernel, opacity 0.1, no higher SH) and are fitted to the views
+with densify= on both backends: the loss of the first and last passes and the PSNR of the views before and after."""
 import argparse
 import importlib
 import os
@@ -66,6 +71,32 @@ def densify_demo(pkg, fit, scene, images, c2w, K, args):
               f"{float(h[-tail:].mean()):.5f}; status {int(rep['status'])}; rounds (iteration, n, clones, splits, pruned, n after): {rounds}")
 
 
+def psnr(render, scene, held):
+    """Mean over the views of 10 log10(1 / MSE) between the scene's rasterised views and the targets, on [0, 1]."""
+    out = render.render_views(scene, held, renderer="raster")
+    diff = [(np.asarray(a.image[..., :3], np.float64) - np.asarray(b.image[..., :3], np.float64)) / 255.0 for a, b in zip(out, held)]
+    mse = [float((d * d).mean()) for d in diff]
+    return float(np.mean([10.0 * np.log10(1.0 / max(m, 1e-12)) for m in mse]))
+
+
+def from_points_demo(pkg, fit, scene, held, images, c2w, K, args):
+    render = importlib.import_module("6dgs_amd.render")
+    n = min(args.from_points, len(scene))
+    idx = torch.randperm(len(scene), generator=torch.Generator().manual_seed(args.seed))[:n].sort().values.to(scene._xyz.device)
+    colors = (scene._features_dc[idx, 0, :] * 0.28209479177387814 + 0.5).clamp(0.0, 1.0)
+    start = pkg.GaussianScene.from_points(scene._xyz[idx], colors, scene.max_sh_degree)
+    opts = dict(from_iter=args.from_iter, until_iter=args.until_iter, interval=args.interval, grad_threshold=args.grad)
+    sigma = torch.exp(start._scaling[:, 0])
+    print(f"{n} of {len(scene)} centres -> from_points: scale quantiles 10 / 50 / 90 % {', '.join(f'{float(q):.4f}' for q in sigma.quantile(torch.tensor([0.1, 0.5, 0.9], device=sigma.device)))}; "
+          f"{args.views} views of {args.size} x {args.size}, {args.steps} steps; densify {opts}; PSNR before {psnr(render, start, held):.2f} dB")
+    tail = max(min(args.views // args.batch, args.steps), 1)
+    for backend in ("fused", "torch"):
+        new, rep = fit.fit_scene(start, images, c2w, K, steps=args.steps, batch=args.batch, backend=backend, densify=opts, sh_degree_start=0)
+        h = rep["loss_history"]
+        print(f"{backend}: n {len(start)} -> {len(new)}; loss, mean of the first {tail} steps {float(h[:tail].mean()):.5f}, of the last {tail} "
+              f"{float(h[-tail:].mean()):.5f}; PSNR after {psnr(render, new, held):.2f} dB; status {int(rep['status'])}; rounds {rep['rounds'].tolist()}")
+
+
 def rms(a, b):
     return {k: float((getattr(a, attr) - getattr(b, attr)).pow(2).mean().sqrt()) for k, attr in ATTR.items()}
 
@@ -84,6 +115,7 @@ def main():
     ap.add_argument("--position", type=float, default=0.002, help="noise on xyz")
     ap.add_argument("--log_scale", type=float, default=0.05, help="noise on the log-scales")
     ap.add_argument("--densify", action="store_true", help="fit a thinned copy back, with and without densification")
+    ap.add_argument("--from-points", dest="from_points", type=int, default=0, help="start from this many of the stand-in's centres (from_points)")
     ap.add_argument("--keep", type=float, default=0.5, help="--densify: the share of the Gaussians kept")
     ap.add_argument("--enlarge", type=float, default=1.5, help="--densify: the factor on the kept Gaussians' scales")
     ap.add_argument("--from_iter", type=int, default=5)
@@ -101,6 +133,8 @@ def main():
     c2w, K, images = torch.stack(c2w), torch.stack(Ks), [c.image for c in held]
     if args.densify:
         return densify_demo(pkg, fit, scene, images, c2w, K, args)
+    if args.from_points:
+        return from_points_demo(pkg, fit, scene, held, images, c2w, K, args)
     start = perturbed(pkg, scene, {"f_dc": args.colour, "opacity": args.opacity, "xyz": args.position, "scale": args.log_scale}, args.seed)
     print(f"{args.gaussians} Gaussians, {args.views} views of {args.size} x {args.size}, {args.steps} steps of {args.batch}, {args.rounds} rounds")
     ms, out = {"torch": [], "fused": []}, {}
