@@ -66,6 +66,11 @@ SIGNATURES = {
     "sixdgs_refine_poses_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
     "sixdgs_refine_poses": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, i32, i32, C.c_float, vp, vp, i32, i32, C.c_float,
                                   i32, C.c_float, C.c_float, C.c_float, C.c_float, i64] + [vp] * 7 + [vp, sz, vp]),
+    "sixdgs_target_pyramid": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
+    "sixdgs_pose_rebase": (i32, [vp, vp, i32, vp, vp]),
+    "sixdgs_refine_poses_levels_workspace_bytes": (sz, [i64, i32, i32, vp, vp, vp]),
+    "sixdgs_refine_poses_levels": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, C.c_float, vp, C.c_float, i32] + [vp] * 7
+                                   + [C.c_float, C.c_float, C.c_float] + [vp] * 8 + [vp, sz, vp]),
     "sixdgs_gaussian_adam": (i32, [i64, i32, i32] + [vp] * 6 + [vp] * 6 + [vp, vp, vp, C.c_float, C.c_float, C.c_float, vp, i64, vp, vp]),
     "sixdgs_opacity_reset": (i32, [vp, i64, i32, vp, vp, C.c_float, vp]),
     "sixdgs_fit_scene_workspace_bytes": (sz, [i64, i32, i32, i32, i32, i64]),

@@ -2,7 +2,8 @@
 // arithmetic of the ray-MLP chain's operand planes), of pose_step.h (the per-view arithmetic of pose refinement) and of adam_step.h
 // (the per-entry arithmetic of fitting a scene's Gaussians) behind a tiny C ABI, so the CPU test-suite can compare the product's arithmetic with the oracle and the
 // golden vectors without a GPU.  densify_rules.h (the per-entry rules of a densification round) and knn_rules.h (the pair and box rules
-// of the 3-nearest-neighbour search) are instantiated here too.  Contains no kernels; never used by the product path.
+// of the 3-nearest-neighbour search) are instantiated here too, and pyramid_rules.h (a level schedule's geometry, target value and
+// keep-the-input rule).  Contains no kernels; never used by the product path.
 #include <stdlib.h>
 
 #include "device_math.h"
@@ -13,6 +14,7 @@
 #include "adam_step.h"
 #include "densify_rules.h"
 #include "knn_rules.h"
+#include "pyramid_rules.h"
 
 #include <algorithm>
 #include <vector>
@@ -319,6 +321,45 @@ int hc_knn_boxed(long long n, const float* xyz, int box, float* mean_d2, int* vi
     if (visited) visited[order[k]] = walked;
   }
   return 0;
+}
+// ---- pyramid_rules.h: the rules of a level schedule (tests/test_pyramid_host.py) ----
+int hc_pyr_max_levels() { return pyr::kMaxLevels; }
+int hc_pyr_max_downscale() { return pyr::kMaxDownscale; }
+// geo4 = (w, h, ox, oy); k_out4 = the level's intrinsics of k4 = (fx, fy, cx, cy)
+void hc_pyr_geometry(int W, int H, int d, const float* k4, int* geo4, float* k_out4) {
+  const pyr::Level g = pyr::level_geometry(W, H, d);
+  geo4[0] = g.w; geo4[1] = g.h; geo4[2] = g.ox; geo4[3] = g.oy;
+  pyr::level_intrinsics(k4, d, g.ox, g.oy, k_out4);
+}
+// sixdgs_target_pyramid's one level on the host: images [views][H][W][C] -> out [views][h][w][3]; -1 where the entry point refuses
+int hc_pyr_target(const unsigned char* images, int views, int H, int W, int C, int composite, const float* background, int d, float* out) {
+  if (d < 1 || d > pyr::kMaxDownscale || (C != 3 && C != 4) || (composite && C != 4)) return -1;
+  const pyr::Level g = pyr::level_geometry(W, H, d);
+  if (g.w < 1 || g.h < 1) return -1;
+  float bg255[3] = {0.f, 0.f, 0.f};
+  if (composite)
+    for (int c = 0; c < 3; ++c) bg255[c] = pyr::background_term(background[c]);
+  for (int v = 0; v < views; ++v)
+    for (int y = 0; y < g.h; ++y)
+      for (int x = 0; x < g.w; ++x)
+        for (int c = 0; c < 3; ++c) {
+          unsigned S = 0u, S2 = 0u;
+          for (int j = 0; j < d; ++j)
+            for (int i = 0; i < d; ++i) {
+              const unsigned char* q = images + (((size_t)v * H + (size_t)(g.oy + y * d + j)) * W + (size_t)(g.ox + x * d + i)) * C;
+              if (composite) {
+                S += (unsigned)q[c] * (unsigned)q[3];
+                S2 += 255u - (unsigned)q[3];
+              } else {
+                S += (unsigned)q[c];
+              }
+            }
+          out[(((size_t)v * g.h + y) * g.w + x) * 3 + c] = composite ? pyr::value_composite(S, S2, bg255[c], d) : pyr::value_plain(S, d);
+        }
+  return 0;
+}
+void hc_pyr_keep_input(const float* best_loss_last, const float* loss_input, long long n, int* keep) {
+  for (long long i = 0; i < n; ++i) keep[i] = pyr::keep_input(best_loss_last[i], loss_input[i]) ? 1 : 0;
 }
 int hc_dl_const(int which) {
   const int v[] = {dl::kSlabB, dl::kPRow, dl::kGran, dl::kGranSlab, dl::kChunkRun};

@@ -714,6 +714,171 @@ def refine_poses_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, sta
     return out
 
 
+# a coarse-to-fine level schedule (csrc/pyramid_rules.h states the limits)
+PYRAMID_MAX_LEVELS, PYRAMID_MAX_DOWNSCALE, PYRAMID_MAX_SIDE = 8, 256, 32768
+
+
+def pyramid_geometry(width: int, height: int, downscale: int):
+    """(w, h, crop_x, crop_y) of the level of `downscale` of a width x height query: w = width // d, h = height // d and the centred crop
+    to a multiple of d (LEVEL GEOMETRY in include/sixdgs.h).  Needs no GPU."""
+    d = int(downscale)
+    w, h = int(width) // d, int(height) // d
+    return w, h, (int(width) - w * d) // 2, (int(height) - h * d) // 2
+
+
+def _host(ctype, values):
+    """A host array of `ctype` for an entry point that reads it at the call -> (the array, which the caller keeps alive; its pointer)."""
+    a = (ctype * len(values))(*values)
+    return a, C.cast(a, C.c_void_p)
+
+
+@_on_device
+def target_pyramid(images_u8: torch.Tensor, downscales, *, composite: bool = False, background=(1.0, 1.0, 1.0), out=None) -> list:
+    """The targets of a level schedule (sixdgs_target_pyramid in include/sixdgs.h): images_u8 uint8 [V,H,W,3|4] on the GPU and up to 8
+    downscales d -> a list of fp32 [V,H // d,W // d,3], each pixel the mean of a d x d block of the centred crop, composited over
+    `background` first when `composite` (which needs four channels).  One streaming kernel per level; the same bytes on every call.
+    out: the tensors to write (contiguous fp32 of those shapes), else new ones."""
+    if not torch.is_tensor(images_u8) or images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[3] not in (3, 4):
+        raise ValueError("images_u8 must be a uint8 [V,H,W,3|4] tensor")
+    if not images_u8.is_contiguous():
+        raise ValueError("images_u8 must be contiguous")
+    views, height, width, channels = (int(x) for x in images_u8.shape)
+    downscales = list(downscales)
+    if any(isinstance(d, bool) or int(d) != d for d in downscales):
+        raise ValueError(f"downscales must be integers (got {downscales})")
+    ds = [int(d) for d in downscales]
+    if not 1 <= len(ds) <= PYRAMID_MAX_LEVELS:
+        raise ValueError(f"1 to {PYRAMID_MAX_LEVELS} levels (got {len(ds)})")
+    if composite and channels != 4:
+        raise ValueError("compositing needs a four-channel image")
+    if len(background) != 3:
+        raise ValueError("background must have 3 entries")
+    if not 1 <= width <= PYRAMID_MAX_SIDE or not 1 <= height <= PYRAMID_MAX_SIDE:
+        raise ValueError(f"width and height must be in [1, {PYRAMID_MAX_SIDE}] (got {width} x {height})")
+    shapes = []
+    for d in ds:
+        if not 1 <= d <= PYRAMID_MAX_DOWNSCALE:
+            raise ValueError(f"a downscale must be in [1, {PYRAMID_MAX_DOWNSCALE}] (got {d})")
+        w, h, _, _ = pyramid_geometry(width, height, d)
+        if w < 1 or h < 1:
+            raise ValueError(f"downscale {d} leaves nothing of a {width} x {height} image")
+        shapes.append((views, h, w, 3))
+    _need_gpu(images_u8)
+    if out is None:
+        out = [torch.empty(s, dtype=torch.float32, device=images_u8.device) for s in shapes]
+    out = list(out)
+    if len(out) != len(ds) or any(not torch.is_tensor(o) or tuple(o.shape) != s or o.dtype != torch.float32 or not o.is_contiguous()
+                                  for o, s in zip(out, shapes)):
+        raise ValueError(f"out must be contiguous float32 tensors of shapes {shapes}")
+    _need_gpu(images_u8, *out)
+    keep = [_host(C.c_float, [float(b) for b in background]), _host(C.c_int32, ds), _host(C.c_void_p, [o.data_ptr() for o in out])]
+    check(_lib.load().sixdgs_target_pyramid(_p(images_u8), views, height, width, channels, int(bool(composite)), keep[0][1], len(ds),
+                                            keep[1][1], keep[2][1], _stream()), "target_pyramid")
+    return out
+
+
+@_on_device
+def pose_rebase(rows: torch.Tensor, intrinsics: torch.Tensor) -> torch.Tensor:
+    """rows_out [V,16] = (the 12 w2c entries of rows [V,16], intrinsics [V,4]): a copy of bits (sixdgs_pose_rebase).  It starts a level
+    of a schedule from another level's camera."""
+    _check_rows(rows, "rows")
+    _check_rows(intrinsics, "intrinsics", 4)
+    if intrinsics.shape[0] != rows.shape[0]:
+        raise ValueError("rows and intrinsics disagree about the number of views")
+    _need_gpu(rows, intrinsics)
+    out = torch.empty_like(rows)
+    check(_lib.load().sixdgs_pose_rebase(_p(rows), _p(intrinsics), rows.shape[0], _p(out), _stream()), "pose_rebase")
+    return out
+
+
+def refine_poses_levels_workspace_bytes(n: int, views: int, sizes, max_instances) -> int:
+    """sixdgs_refine_poses_levels_workspace_bytes for levels of sizes [(width, height), ...] and their capacities; needs no GPU."""
+    w, h, cap = _host(C.c_int32, [int(s[0]) for s in sizes]), _host(C.c_int32, [int(s[1]) for s in sizes]), _host(C.c_int64, [int(c) for c in max_instances])
+    return int(_lib.load().sixdgs_refine_poses_levels_workspace_bytes(int(n), int(views), len(sizes), w[1], h[1], cap[1]))
+
+
+@_on_device
+def refine_poses_levels_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, start_rows: torch.Tensor, levels, *,
+                            lambda_dssim: float = 0.2, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, scale_modifier: float = 1.0,
+                            background=(1.0, 1.0, 1.0), scale_is_log: bool = True, opacity_is_logit: bool = True, retry: bool = True) -> dict:
+    """A coarse-to-fine schedule of render-and-compare refinement as ONE library call (sixdgs_refine_poses_levels in include/sixdgs.h).
+    start_rows [V,16] carry the LAST level's intrinsics.  levels: up to 8 dicts, coarse to fine, each with width, height, steps, lr,
+    target (fp32 [V,height,width,3], contiguous), intrinsics ([V,4]) and optionally max_instances (else raster_instances_estimate's).
+    Returns a dict: out_rows [V,16] (the last level's best camera, or start_rows' bits where kept_input), loss_input [V] (the input's
+    loss at the last level), kept_input [V] (int32), best_loss and best_step [L,V], history (a list of [steps_l + 1,V] views of one
+    buffer), status [V] (int32, bits as refine_poses_raw's, carried across the levels), instances_needed and max_instances (lists of int
+    per level).  Reads status and the counts once at the end and -- with retry -- on bit 1 runs again with 5/4 of what each overflowed
+    level needed, at most REFINE_ATTEMPTS runs in all, then RuntimeError."""
+    lam = _lambda(lambda_dssim)
+    levels = [dict(lv) for lv in levels]
+    if not 1 <= len(levels) <= PYRAMID_MAX_LEVELS:
+        raise ValueError(f"1 to {PYRAMID_MAX_LEVELS} levels (got {len(levels)})")
+    scene, n, n_coef = _scene(xyz, scale, rot, opacity, f_dc, f_rest)
+    rows, views, capacities = None, 0, []
+    for i, lv in enumerate(levels):
+        steps = lv.get("steps")
+        if steps is None or isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+            raise ValueError(f"level {i}: steps must be a positive integer (got {steps})")
+        _check_adam(lv.get("lr", float("nan")), beta1, beta2, eps)
+        rows, lv["width"], lv["height"] = _view_args(start_rows, lv.get("width", 0), lv.get("height", 0), background, scale_modifier, "start_rows")
+        views = rows.shape[0]
+        lv["steps"], lv["lr"] = int(steps), float(lv["lr"])
+        lv["target"], is_u8, stride = _target_args(lv.get("target"), views, lv["height"], lv["width"])
+        if is_u8 or stride != 3:
+            raise ValueError(f"level {i}: the target must be float32 with 3 channels")
+        _check_rows(lv.get("intrinsics"), f"level {i}: intrinsics", 4)
+        if lv["intrinsics"].shape[0] != views:
+            raise ValueError(f"level {i}: intrinsics disagree about the number of views")
+        capacities.append(_capacity(lv.get("max_instances"), n, views))
+    start_rows = rows
+    _need_gpu(*scene, start_rows, *[lv["target"] for lv in levels], *[lv["intrinsics"] for lv in levels])
+    lib = _lib.load()
+    dev = scene[0].device
+    bg = _background(background, dev)
+    k = len(levels)
+    first = [0]
+    for lv in levels:
+        first.append(first[-1] + lv["steps"] + 1)
+    out = {"out_rows": torch.empty(views, 16, device=dev), "loss_input": torch.empty(views, device=dev),
+           "kept_input": torch.empty(views, dtype=torch.int32, device=dev), "best_loss": torch.empty(k, views, device=dev),
+           "best_step": torch.empty(k, views, dtype=torch.int32, device=dev), "status": torch.empty(views, dtype=torch.int32, device=dev)}
+    history = torch.empty(first[-1], views, device=dev)
+    needed_t = torch.zeros(k, dtype=torch.int64, device=dev)
+    needed = [0] * k
+    h = {name: _host(ctype, [lv[name] for lv in levels]) for name, ctype in (("width", C.c_int32), ("height", C.c_int32), ("steps", C.c_int32),
+                                                                                ("lr", C.c_float))}
+    h_target = _host(C.c_void_p, [lv["target"].data_ptr() for lv in levels])
+    h_intr = _host(C.c_void_p, [lv["intrinsics"].data_ptr() for lv in levels])
+    for attempt in range(REFINE_ATTEMPTS):
+        h_cap = _host(C.c_int64, capacities)
+        need = lib.sixdgs_refine_poses_levels_workspace_bytes(n, views, k, h["width"][1], h["height"][1], h_cap[1])
+        if need == 0:
+            raise ValueError(f"sizes outside the rasteriser's limits (n {n}, views {views}, levels {[(lv['width'], lv['height']) for lv in levels]}, "
+                             f"instances {capacities})")
+        ws, ws_bytes = _workspace(None, need, dev)
+        check(lib.sixdgs_refine_poses_levels(*_scene_args(scene, n_coef, scale_is_log, opacity_is_logit), int(sh_degree), int(n_coef), n,
+                                             _p(start_rows), views, float(scale_modifier), _p(bg), lam, k, h["width"][1], h["height"][1],
+                                             h["steps"][1], h["lr"][1], h_target[1], h_intr[1], h_cap[1], float(beta1), float(beta2), float(eps),
+                                             _p(out["out_rows"]), _p(out["loss_input"]), _p(out["kept_input"]), _p(out["best_loss"]),
+                                             _p(out["best_step"]), _p(needed_t), _p(history), _p(out["status"]), _p(ws), ws_bytes, _stream()),
+              "refine_poses_levels")
+        if views == 0:
+            break
+        # the one host read of the call: every status word and every level's largest instance count
+        flags = torch.cat([out["status"].to(torch.int64), needed_t]).cpu()
+        needed = [int(x) for x in flags[views:]]
+        if not retry or not bool((flags[:views] & POSE_STATUS_CAPACITY).any()):
+            break
+        if attempt == REFINE_ATTEMPTS - 1 or max(needed) > RASTER_MAX_INSTANCES:
+            raise RuntimeError(f"6dgs_amd: refine_poses_levels still needs {needed} tile instances after {attempt + 1} runs (limit 2^31 - 1): "
+                               "refine fewer views at once")
+        capacities = [_grown(nd) if nd > cap else cap for nd, cap in zip(needed, capacities)]
+    out["history"] = [history[first[i]:first[i + 1]] for i in range(k)]
+    out["instances_needed"] = needed
+    out["max_instances"] = list(capacities)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # fitting a scene's Gaussians below the C ABI
 # ---------------------------------------------------------------------------------------------

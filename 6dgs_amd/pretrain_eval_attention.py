@@ -20,6 +20,9 @@ weights when no checkpoint exists (smoke runs); --n_iterations shortens training
 --refine_steps N (with --refine_downscale, --refine_lr, --refine_lambda, --refine_backend) refines every estimated pose by render-and-compare
 (refine.refine_results) on each rank's block and adds the refined_* and photometric_loss_* keys to its result dicts; the mean and
 median errors before and after go to <out_path>.refine_summary.json.  0, the default: no refinement, results.json as without the flag.
+--refine_levels "8:30:4e-3,4:30:2e-3,2:40:1e-3" (downscale:steps:lr per level, coarse to fine) refines with that level schedule instead
+(refine.refine_poses(levels=...): --refine_steps, --refine_lr and --refine_downscale are not used, and giving --refine_downscale beside
+it is an error); off by default.
 """
 from __future__ import annotations
 
@@ -38,7 +41,7 @@ from .datasets import dotdict, get_checkpoint_arguments, load_data, parse_exp_di
 from .distance_based_loss import DistanceBasedScoreLoss
 from .identification_module import IdentificationModule
 from .sampling import generate_all_possible_rays
-from .refine import refine_results
+from .refine import level_plan, parse_levels, refine_results
 from .scene import GaussianScene
 from .test import test_pose_estimation
 from .train import train_id_module
@@ -78,13 +81,31 @@ def parse_args(argv=None):
                          "per scene.  -1: everything free but 56 GB; 0 (default): off")
     ap.add_argument("--refine_steps", type=int, default=0,
                     help="refine each estimated pose by render-and-compare for this many Adam steps (refine.refine_poses); 0 = off")
-    ap.add_argument("--refine_downscale", type=int, default=4, help="refinement compares at 1 / this of the query's resolution")
+    downscale_given = []
+
+    class NoteGiven(argparse.Action):                  # the default stays 4 in the namespace; --refine_levels needs to know it was typed
+        def __call__(self, parser, namespace, values, option_string=None):
+            downscale_given.append(option_string)
+            setattr(namespace, self.dest, values)
+
+    ap.add_argument("--refine_downscale", type=int, default=4, action=NoteGiven, help="refinement compares at 1 / this of the query's resolution")
     ap.add_argument("--refine_lr", type=float, default=2e-3, help="Adam step of the refinement")
     ap.add_argument("--refine_lambda", type=float, default=0.2, help="weight of D-SSIM in the refinement's loss (the reference's lambda_dssim)")
     # (absent from the namespace unless given: a command line without it parses to exactly what it did before the flag existed)
     ap.add_argument("--refine_backend", choices=("torch", "fused"), default=argparse.SUPPRESS,
                     help="the refinement's loop: torch (default; autograd and Adam around the kernels) or fused (one library call, sixdgs_refine_poses)")
+    ap.add_argument("--refine_levels", type=str, default=argparse.SUPPRESS,
+                    help='refine with a coarse-to-fine level schedule, downscale:steps:lr per level, e.g. "8:30:4e-3,4:30:2e-3,2:40:1e-3" '
+                         "(refine.refine_poses(levels=...)); excludes --refine_downscale")
     args, rest = ap.parse_known_args(argv)
+    if hasattr(args, "refine_levels"):
+        if downscale_given:
+            ap.error("--refine_levels and --refine_downscale exclude each other")
+        try:
+            args.refine_levels = parse_levels(args.refine_levels)
+            level_plan(args.refine_levels, 1 << 15, 1 << 15)      # everything but the image's size, which each scene brings
+        except ValueError as e:
+            ap.error(f"--refine_levels: {e}")
     if args.refine_steps < 0:
         ap.error("--refine_steps must be >= 0 (0 = no refinement)")
     if args.refine_downscale < 1:
@@ -279,8 +300,10 @@ def main(argv=None, backbone: Optional[torch.nn.Module] = None) -> List[dict]:
                 batched_window=args.batched_window, data_parallel_train=args.data_parallel_train,
                 backward_ray_groups=args.backward_ray_groups, pose_solver=args.pose_solver, inlier_scale=args.inlier_scale,
                 rays_to_output=args.rays_to_output,
-                refine=dict(steps=args.refine_steps, lr=args.refine_lr, lambda_dssim=args.refine_lambda, downscale=args.refine_downscale,
-                            backend=getattr(args, "refine_backend", "torch"))
+                refine=dict(levels=args.refine_levels, lambda_dssim=args.refine_lambda, backend=getattr(args, "refine_backend", "torch"))
+                if hasattr(args, "refine_levels") else
+                dict(steps=args.refine_steps, lr=args.refine_lr, lambda_dssim=args.refine_lambda, downscale=args.refine_downscale,
+                     backend=getattr(args, "refine_backend", "torch"))
                 if args.refine_steps > 0 else None)
             if rank == 0:
                 results.extend(obj)
@@ -293,7 +316,7 @@ def main(argv=None, backbone: Optional[torch.nn.Module] = None) -> List[dict]:
         print("Saving results")
         with open(out_path_abs, "w") as fh:
             json.dump(results, fh)
-        if args.refine_steps > 0:
+        if args.refine_steps > 0 or hasattr(args, "refine_levels"):
             with open(out_path_abs + ".refine_summary.json", "w") as fh:
                 json.dump(refine_summary(results), fh)
     dd.barrier()

@@ -17,6 +17,15 @@ The parametrisation is tools/raster_fit.py's: delta = (translation, axis-angle) 
 delta = 0 is the starting pose and the step size means the same thing wherever the camera stands.  The target is the query image
 averaged over downscale x downscale blocks (a centred crop to a multiple of downscale first), and the intrinsics follow:
 fx / d, fy / d, (cx - crop_x) / d, (cy - crop_y) / d -- a pixel's centre is at (x + 0.5, y + 0.5) in both images.
+
+    level_plan(levels, W, H)                          a coarse-to-fine schedule [(downscale, steps, lr), ...] checked, with its geometry
+    refine_poses(..., levels=[(8, 30, 4e-3), ...])    the loop above once per level, each level started from the one before's best pose
+
+With `levels` the targets of all levels come from one kernel (ops.target_pyramid -> sixdgs_target_pyramid) on both backends, the pose
+arithmetic of both is the library's (ops.pose_step on the torch side, under autograd's image and loss), the input
+pose's loss is taken at the last level first, and a view whose last level did not end below that loss keeps its input pose: a coarse
+level can carry a pose somewhere worse at full resolution, and this is what stops it.  "fused" runs the whole schedule as one library
+call (ops.refine_poses_levels_raw -> sixdgs_refine_poses_levels).
 """
 from __future__ import annotations
 
@@ -28,6 +37,7 @@ import torch
 from . import autograd, ops
 
 BACKENDS = ("torch", "fused")
+DEFAULT_DOWNSCALE = 4
 ALPHA_MODES = ("ignore", "composite")
 
 
@@ -162,21 +172,149 @@ def posed_views(images, c2w, K, dev, downscale: int, alpha: str, background):
 
 def _rows_to_c2w(best_rows: torch.Tensor, best_step: torch.Tensor, c2w: torch.Tensor) -> torch.Tensor:
     """The c2w [V,4,4] of the best camera rows (inverted on the host); the input pose itself where the best step is 0."""
+    return _rows_to_c2w_unless(best_rows, best_step == 0, c2w)
+
+
+def _rows_to_c2w_unless(rows: torch.Tensor, keep: torch.Tensor, c2w: torch.Tensor) -> torch.Tensor:
+    """The c2w [V,4,4] of the camera rows (inverted on the host); the input pose c2w itself, bit for bit, where `keep` [V] is set."""
     views, dev = c2w.shape[0], c2w.device
     w2c = torch.eye(4).repeat(views, 1, 1)
-    w2c[:, :3, :] = best_rows[:, :12].reshape(views, 3, 4).cpu()
-    return torch.where((best_step == 0)[:, None, None], c2w, torch.linalg.inv(w2c).to(dev))
+    w2c[:, :3, :] = rows[:, :12].reshape(views, 3, 4).cpu()
+    return torch.where(keep.to(dev)[:, None, None], c2w, torch.linalg.inv(w2c).to(dev))
 
 
-def refine_poses(scene, images, c2w, intrinsics, *, steps: int = 100, lr: float = 2e-3, lambda_dssim: float = 0.2, downscale: int = 4,
-                 background=(1.0, 1.0, 1.0), scale_modifier: float = 1.0, backend: str = "torch", alpha: str = "ignore") -> dict:
+MAX_LEVELS, MAX_DOWNSCALE = ops.PYRAMID_MAX_LEVELS, ops.PYRAMID_MAX_DOWNSCALE
+
+
+def parse_levels(text: str):
+    """"8:30:4e-3,4:30:2e-3,2:40:1e-3" -> [(8, 30, 4e-3), (4, 30, 2e-3), (2, 40, 1e-3)]: downscale:steps:lr per level, coarse to fine."""
+    out = []
+    for part in str(text).split(","):
+        fields = part.strip().split(":")
+        if len(fields) != 3:
+            raise ValueError(f"a level is downscale:steps:lr (got {part!r})")
+        try:
+            out.append((int(fields[0]), int(fields[1]), float(fields[2])))
+        except ValueError:
+            raise ValueError(f"a level is downscale:steps:lr with two integers and a number (got {part!r})") from None
+    return out
+
+
+def level_plan(levels, width: int, height: int) -> List[dict]:
+    """Check a level schedule for a width x height query and give its geometry.  levels: 1 to 8 entries (downscale, steps, lr), in the
+    order they run (coarse to fine); downscale an integer in [1, 256] that leaves at least one pixel of the image, steps an integer
+    >= 1, lr positive and finite.  Returns per level a dict: downscale, steps, lr, width, height (of the level's image), crop_x, crop_y
+    (where its centred crop starts in the query) -- prepare_target's and scaled_intrinsics' numbers.  Needs no GPU."""
+    try:
+        levels = [tuple(lv) for lv in levels]
+    except TypeError:
+        raise ValueError(f"levels must be a sequence of (downscale, steps, lr) (got {levels!r})") from None
+    if not 1 <= len(levels) <= MAX_LEVELS:
+        raise ValueError(f"levels must have 1 to {MAX_LEVELS} entries (got {len(levels)})")
+    if int(width) < 1 or int(height) < 1:
+        raise ValueError(f"width and height must be positive (got {width} x {height})")
+    plan = []
+    for i, lv in enumerate(levels):
+        if len(lv) != 3:
+            raise ValueError(f"level {i} must be (downscale, steps, lr) (got {lv!r})")
+        d, steps, lr = lv
+        for name, x in (("downscale", d), ("steps", steps)):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) < 1:
+                raise ValueError(f"level {i}: {name} must be a positive integer (got {x!r})")
+        if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not (float(lr) > 0.0 and float(lr) < float("inf")):
+            raise ValueError(f"level {i}: lr must be positive and finite (got {lr!r})")
+        d, steps = int(d), int(steps)
+        if d > MAX_DOWNSCALE:
+            raise ValueError(f"level {i}: downscale must be at most {MAX_DOWNSCALE} (got {d})")
+        w, h, ox, oy = ops.pyramid_geometry(width, height, d)
+        if w < 1 or h < 1:
+            raise ValueError(f"level {i}: downscale {d} leaves nothing of a {width} x {height} image")
+        plan.append({"downscale": d, "steps": steps, "lr": float(lr), "width": w, "height": h, "crop_x": ox, "crop_y": oy})
+    return plan
+
+
+def _image_size(images):
+    """(width, height) of the first image, without moving anything."""
+    first = images[0] if not (torch.is_tensor(images) and images.dim() == 3) else images
+    shape = tuple(first.shape) if hasattr(first, "shape") else np.asarray(first).shape
+    if len(shape) != 3:
+        raise ValueError(f"images must be uint8 [H,W,3|4] (got shape {shape})")
+    return int(shape[1]), int(shape[0])
+
+
+def _refine_levels(tensors, sh_degree, images, c2w, K, dev, plan, lambda_dssim, background, scale_modifier, backend, alpha) -> dict:
+    """refine_poses with a level plan: the targets of every level from ops.target_pyramid, then the schedule on either backend."""
+    views = c2w.shape[0]
+    stacked = _stack_images(images, dev)
+    composite = alpha == "composite" and stacked.shape[3] == 4
+    targets = ops.target_pyramid(stacked, [lv["downscale"] for lv in plan], composite=composite, background=background)
+    intr = [scaled_intrinsics(K.cpu(), lv["downscale"], lv["crop_x"], lv["crop_y"]).to(dev).contiguous() for lv in plan]
+    start_rows = torch.cat([torch.linalg.inv(c2w.cpu())[:, :3, :].reshape(views, 12).to(dev), intr[-1]], dim=1).contiguous()
+    c2w = c2w.to(dev)
+    kw = dict(background=background, scale_modifier=scale_modifier)
+    if backend == "fused":
+        raw = ops.refine_poses_levels_raw(*tensors, sh_degree, start_rows,
+                                          [dict(width=lv["width"], height=lv["height"], steps=lv["steps"], lr=lv["lr"], target=t, intrinsics=k)
+                                           for lv, t, k in zip(plan, targets, intr)], lambda_dssim=float(lambda_dssim), **kw)
+        kept = raw["kept_input"] != 0
+        return {"c2w": _rows_to_c2w_unless(raw["out_rows"], kept, c2w), "loss_start": raw["loss_input"].clone(), "loss_best": raw["best_loss"][-1].clone(),
+                "best_step": raw["best_step"][-1].to(torch.int64), "loss_history": [h.clone() for h in raw["history"]], "levels": plan,
+                "loss_input": raw["loss_input"], "kept_input": kept, "level_loss_best": raw["best_loss"],
+                "level_best_step": raw["best_step"].to(torch.int64), "status": raw["status"]}
+    # the torch arm: autograd draws and compares, step by step from the host; the pose arithmetic and its rules are sixdgs_pose_step's,
+    # the library's own, so both arms move a view by the same bits and a level starts from the same camera in both
+    with torch.no_grad():
+        image = autograd.raster_views(*tensors, sh_degree, start_rows, plan[-1]["width"], plan[-1]["height"], **kw)
+        loss_input = autograd.photometric_loss(image, targets[-1], lambda_dssim)
+    status = torch.zeros(views, dtype=torch.int32, device=dev)
+    histories, level_best, level_step = [], [], []
+    carried = start_rows
+    for lv, target, k in zip(plan, targets, intr):
+        start = ops.pose_rebase(carried, k)
+        state = ops.pose_state(start)                        # delta, m, v and best_* fresh; status carried
+        state["status"] = status
+        history = torch.empty(lv["steps"] + 1, views, device=dev)
+        for step in range(lv["steps"] + 1):
+            last = step == lv["steps"]
+            rows = state["rows"].detach().clone().requires_grad_(not last)
+            with torch.set_grad_enabled(not last):
+                image = autograd.raster_views(*tensors, sh_degree, rows, lv["width"], lv["height"], **kw)
+                loss = autograd.photometric_loss(image, target, lambda_dssim)
+            d_rows = None if last else torch.autograd.grad(loss.sum(), rows)[0].contiguous()
+            ops.pose_step(start, loss.detach().contiguous(), d_rows, state, history[step], step, evaluate_only=last, lr=lv["lr"])
+        histories.append(history)
+        level_best.append(state["best_loss"])
+        level_step.append(state["best_step"].to(torch.int64))
+        carried = state["best_rows"]
+    kept = ~(level_best[-1] < loss_input)                   # a NaN on either side and a tie keep the input
+    return {"c2w": _rows_to_c2w_unless(carried, kept, c2w), "loss_start": loss_input.clone(), "loss_best": level_best[-1].clone(),
+            "best_step": level_step[-1], "loss_history": histories, "levels": plan, "loss_input": loss_input, "kept_input": kept,
+            "level_loss_best": torch.stack(level_best), "level_best_step": torch.stack(level_step), "status": status}
+
+
+def refine_poses(scene, images, c2w, intrinsics, *, steps: int = 100, lr: float = 2e-3, lambda_dssim: float = 0.2, downscale=None,
+                 background=(1.0, 1.0, 1.0), scale_modifier: float = 1.0, backend: str = "torch", alpha: str = "ignore", levels=None) -> dict:
     """Refine the poses c2w [V,4,4] of the query `images` (uint8 [H,W,3|4] arrays or GPU tensors of one size) against `scene`
     (a GaussianScene on the GPU).  intrinsics: K [3,3] or [V,3,3] as test.gt_pose_and_intrinsics gives it.  Adam (lr) for `steps`
-    steps on [V,6], objective photometric_loss(raster_views(...)).sum() at 1 / downscale of the resolution.
+    steps on [V,6], objective photometric_loss(raster_views(...)).sum() at 1 / downscale of the resolution (downscale None: 4).
     Returns a dict of tensors on the scene's device: c2w [V,4,4] -- per view the iterate with the lowest loss, the input pose itself
     where no step lowered it --, loss_start [V], loss_best [V], best_step [V] (int64) and loss_history [steps + 1, V].
     backend "fused" runs the loop as one library call (ops.refine_poses_raw) and adds status [V] (int32, 0 = fine; bit 0: the view met a
-    loss or gradient that was not finite and stopped moving there).  alpha: prepare_target's, with this call's background."""
+    loss or gradient that was not finite and stopped moving there).  alpha: prepare_target's, with this call's background.
+    levels: None, or a coarse-to-fine schedule [(downscale, steps, lr), ...] (level_plan checks it).  With levels the arguments steps, lr
+    are IGNORED, unchecked, and any downscale beside levels raises ValueError; every level runs the loop above from
+    the level before's best pose with fresh Adam state, and the returned dict changes as follows: loss_start = loss_input [V] is the
+    input pose's loss at the LAST level and loss_best [V] / best_step [V] are the last level's, so the two losses are at one
+    resolution; kept_input [V] (bool) is set where NOT (loss_best < loss_input) -- there c2w is the input pose, bit for bit --;
+    loss_history is a list of per-level [steps_l + 1, V] tensors; level_loss_best and level_best_step are [L, V]; levels is the plan.
+    With levels BOTH backends return status [V], carried across the levels: "torch" draws and compares through autograd step by step
+    from the host and hands the camera rows' gradient to the library's pose step (ops.pose_step), "fused" makes one call; the pose
+    arithmetic is the same code in both, so they give the same iterates.  (Without levels "torch" keeps its own compose and Adam.)"""
+    if levels is not None:
+        if downscale is not None:
+            raise ValueError(f"levels and downscale exclude each other (got downscale {downscale} beside levels)")
+        steps, lr = 1, 1.0                                  # ignored with levels: nothing of them is checked or used
+    downscale = DEFAULT_DOWNSCALE if downscale is None else downscale
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {BACKENDS} (got {backend!r})")
     if alpha not in ALPHA_MODES:
@@ -194,11 +332,14 @@ def refine_poses(scene, images, c2w, intrinsics, *, steps: int = 100, lr: float 
     steps, downscale = int(steps), int(downscale)
     c2w, K = check_poses(images, c2w, intrinsics)
     views = c2w.shape[0]
+    plan = None if levels is None else level_plan(levels, *_image_size(images))
     tensors, sh_degree = _scene_tensors(scene)
     if not tensors[0].is_cuda:
         raise RuntimeError("6dgs_amd: refine_poses needs the scene on the GPU (no CPU fallback on the product path)")
     dev = tensors[0].device
     tensors = tuple(t.detach() for t in tensors)
+    if plan is not None:
+        return _refine_levels(tensors, sh_degree, images, c2w, K, dev, plan, lambda_dssim, background, scale_modifier, backend, alpha)
     target, start, width, height = posed_views(images, c2w, K, dev, downscale, alpha, background)
     c2w = c2w.to(dev)
     if backend == "fused":

@@ -415,6 +415,71 @@ int sixdgs_refine_poses(const float* xyz, const float* scale, int scale_is_log, 
                         size_t ws_bytes, sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Coarse-to-fine pose refinement (additive in ABI 10): the targets of a level schedule, the hand-over of a camera from one level to
+ * the next, and the whole schedule as one call.  The rules are csrc/pyramid_rules.h's.
+ *
+ * LEVEL GEOMETRY.  A level of downscale d of a W x H query has w = W / d by h = H / d pixels (integer division); pixel (x, y) is the
+ * mean of the d x d block of the query whose corner is (ox + x d, oy + y d), with ox = (W - w d) / 2 and oy = (H - h d) / 2: the
+ * centred crop to a multiple of d.  Its intrinsics are fx / d, fy / d, (cx - ox) / d, (cy - oy) / d, with d, ox and oy converted to
+ * fp32 first.  1 <= d <= 256.
+ *
+ * TARGET VALUE of level pixel (x, y), channel c, from the block's bytes u.  The sums are exact integers; the fp32 expression is
+ * evaluated as written, without contraction into fused multiply-adds.
+ *   without compositing:  S = sum u_c;  value = float(S) / float(255 d d).
+ *   with compositing (four channels; a = the fourth):  S1 = sum u_c u_a,  S2 = sum (255 - u_a),  k = 255.0f * background[c] (once);
+ *     value = (float(S1) + k * float(S2)) / (65025.0f * float(d d)).
+ * With d <= 256, S, S2 and 255 d d stay below 2^24 (exact in fp32) and S1 <= 255^2 2^16 < 2^32 fits 32 unsigned bits.
+ *
+ * sixdgs_target_pyramid reads images uint8 [views][height][width][channels] (channels 3 or 4) and writes, for each of `levels` (1 .. 8)
+ * downscales h_downscale[l] (HOST array), the level's target fp32 [views][h][w][3] to h_out[l] (HOST array of device pointers, 4-byte
+ * aligned).  composite = 1 needs channels == 4 and h_background (HOST [3], finite, read at the call); with composite = 0 the fourth
+ * channel of a four-channel image is never read.  One launch per level of one streaming kernel: per input row a workgroup's bytes are
+ * one contiguous run, read one byte at a time up to the first 16-byte boundary, 16 bytes per lane from there, and byte-wise behind the
+ * last boundary; nothing outside the crop is read; one owner per output, no atomics.  SAME INPUT, SAME BYTES; a view's target does not
+ * depend on the other views of the call.  Limits: views <= 65535, width, height <= 32768.  SIXDGS_E_BADARG without a launch for
+ * argument errors: levels outside 1 .. 8, a d outside 1 .. 256 or with h or w of 0, a NULL or misaligned output.  views == 0 returns 0.
+ *
+ * sixdgs_pose_rebase: rows_out[v] = (the 12 w2c entries of rows_in[v], intrinsics[v][4]), a copy of bits (rows_out may be rows_in).
+ *
+ * sixdgs_refine_poses_levels runs a schedule of `levels` (1 .. 8) levels, coarse to fine, and reads nothing back.  Scene arrays, flags,
+ * scale_modifier, background (device [3]) and lambda as sixdgs_refine_poses takes them; start_rows [views][16] carry the LAST level's
+ * intrinsics.  Per level l, all HOST arrays: h_width[l], h_height[l], h_steps[l] (>= 1), h_lr[l], h_target[l] (device fp32
+ * [views][h_height[l]][h_width[l]][3]), h_intrinsics[l] (device [views][4]) and h_max_instances[l].  It enqueues:
+ *   1. the input's loss: sixdgs_raster_views of start_rows at the last level, sixdgs_photometric_loss without a gradient.
+ *      loss_input[v] is that loss; status[v] starts as 0.  If the instance count exceeds h_max_instances[levels - 1], loss_input[v]
+ *      is NaN and status[v] starts with bit 1 set.
+ *   2. for l = 0 .. levels - 1: start_l = sixdgs_pose_rebase(l == 0 ? start_rows : level l - 1's best_rows, h_intrinsics[l]); then
+ *      exactly the loop of sixdgs_refine_poses from start_l on h_target[l] with h_steps[l], h_lr[l] and h_max_instances[l], where
+ *      delta, m, v, best_loss, best_step and best_rows start fresh (as sixdgs_pose_step describes) and status is CARRIED from the
+ *      level before.  So a capacity overflow at one level freezes every later step of every later level, whose history rows are NaN,
+ *      and a view frozen by bit 0 stays frozen.  The level's history rows are history + (sum over l' < l of (h_steps[l'] + 1)) * views.
+ *      instances_needed[l] (all start as 0) is the largest instance count seen at level l, the count of 1. included in the last.
+ *   3. kept_input[v] = NOT (best_loss[levels - 1][v] < loss_input[v]) -- a NaN on either side and a tie keep the input --;
+ *      out_rows[v] = kept_input[v] ? start_rows[v] : the last level's best_rows[v].
+ * Outputs (device): out_rows [views][16] (not start_rows), loss_input [views], kept_input [views] int32, best_loss and best_step
+ * [levels][views], instances_needed [levels] int64, history [sum (h_steps[l] + 1)][views], status [views].
+ * SAME INPUT, SAME BYTES; row v of every output is the same bits whether view v is refined alone or in a batch, given capacities that
+ * fit.  SIXDGS_E_BADARG for argument errors, SIXDGS_E_WORKSPACE for too small a workspace, both without touching a GPU; views == 0
+ * returns 0.  sixdgs_refine_poses_levels_workspace_bytes is answered without a GPU and is 0 outside the limits: the largest of the
+ * levels' sixdgs_refine_poses_workspace_bytes, plus two sets of camera rows [views][16] (a level's start and its best), each piece
+ * rounded up to 256 B. */
+int sixdgs_target_pyramid(const uint8_t* images, int views, int height, int width, int channels, int composite,
+                          const float* h_background /*host [3] or NULL*/, int levels, const int32_t* h_downscale /*host [levels]*/,
+                          float* const* h_out /*host [levels] of device pointers*/, sixdgs_stream_t stream);
+int sixdgs_pose_rebase(const float* rows_in /*[views][16]*/, const float* intrinsics /*[views][4]*/, int views, float* rows_out /*[views][16]*/,
+                       sixdgs_stream_t stream);
+size_t sixdgs_refine_poses_levels_workspace_bytes(int64_t n, int views, int levels, const int32_t* h_width, const int32_t* h_height,
+                                                  const int64_t* h_max_instances);
+int sixdgs_refine_poses_levels(const float* xyz, const float* scale, int scale_is_log, const float* rot, const float* opacity,
+                               int opacity_is_logit, const float* f_dc, const float* f_rest, int sh_degree, int n_coef, int64_t n,
+                               const float* start_rows /*[views][16]*/, int views, float scale_modifier, const float* background /*[3] device*/,
+                               float lambda, int levels, const int32_t* h_width, const int32_t* h_height, const int32_t* h_steps,
+                               const float* h_lr, const float* const* h_target, const float* const* h_intrinsics,
+                               const int64_t* h_max_instances, float beta1, float beta2, float eps, float* out_rows, float* loss_input,
+                               int32_t* kept_input, float* best_loss, int32_t* best_step, int64_t* instances_needed, float* history,
+                               int32_t* status, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Adam over a scene's Gaussians and the opacity reset (additive in ABI 10): the optimiser's side of fitting a set of Gaussians to
  * posed views (the reference's train.py:94-122 and scene/gaussian_model.py:230-282; n is fixed within a call -- the densification
  * round that changes it is sixdgs_densify, further down).  All arithmetic in fp32, no contraction into fused multiply-adds; one owner

@@ -1,17 +1,20 @@
 """Measure pose refinement (6dgs_amd/refine.py) on a stand-in scene.
 
     python tools/refine_standin.py [--gaussians 5000] [--size 224] [--views 8] [--steps 100] [--downscale 2] [--iterations 600] [--backend torch|fused]
+                                   [--levels 8:30:4e-3,4:30:2e-3,2:40:1e-3]
 
 Builds synthetic.make_scene, renders held-out views with renderer="raster" (so the query images are the scene's own renderer's), and
 refines from two kinds of start:
   perturbed   the true camera moved by tools/raster_fit.py's offset (about 0.054 scene units and 1.5 degrees, signs alternating over the
-              views) and by 4 x that offset
+              views) and by 2 x and 4 x that offset
   estimator   the poses test_pose_estimation gives on a scorer trained on rendered views of the same scene (tools/train_standin.py's
               functions, `iterations` iterations; 0 skips this part)
 Reports per kind the centre and rotation error before and after (median and how many views improved), the loss before and after, and
 the milliseconds of a refinement step split into raster forward, loss, raster backward and the rest (HIP events around each part
 of a hand-written step on the same views; the rest is compose, its autograd, Adam and the host in between).
 --backend fused runs every refinement as one library call (refine_poses(..., backend="fused")); the split is of the torch step either way.
+--levels runs every start a second time with that coarse-to-fine schedule (downscale:steps:lr per level) and prints the two arms one
+under the other, with how many views kept their input pose.
 Nothing is asserted: what comes out is reported, a negative result included."""
 import argparse
 import importlib
@@ -38,7 +41,8 @@ def summarise(name, refine, gt, start, out):
     print(f"{name}: {len(t0)} views; centre error median {float(t0.nanmedian()):.4f} -> {float(t1.nanmedian()):.4f} (max {float(t0.max()):.4f} -> "
           f"{float(t1.max()):.4f}), rotation error median {float(a0.nanmedian()):.3f} -> {float(a1.nanmedian()):.3f} deg (max {float(a0.max()):.3f} -> "
           f"{float(a1.max()):.3f}); both errors fell on {better} views; loss median {float(out['loss_start'].median()):.5f} -> "
-          f"{float(out['loss_best'].median()):.5f}; best step median {int(out['best_step'].median())}")
+          f"{float(out['loss_best'].median()):.5f}; best step median {int(out['best_step'].median())}"
+          + (f"; kept the input on {int(out['kept_input'].sum())} views" if "kept_input" in out else ""), flush=True)
 
 
 def step_split(refine, autograd, ops, scene, images, start, K, downscale, repeats=20):
@@ -84,6 +88,7 @@ def main():
     ap.add_argument("--downscale", type=int, default=2)
     ap.add_argument("--iterations", type=int, default=600, help="training iterations of the stand-in scorer (0: skip the estimator part)")
     ap.add_argument("--backend", choices=("torch", "fused"), default="torch", help="refine.refine_poses' backend")
+    ap.add_argument("--levels", default=None, help="a second arm: a coarse-to-fine schedule, downscale:steps:lr per level, comma separated")
     ap.add_argument("--ckpt", default=os.path.join(tempfile.gettempdir(), "refine_standin_id_module.th"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -97,15 +102,19 @@ def main():
     images = [c.image for c in held]
     rows = torch.from_numpy(importlib.import_module("6dgs_amd.render").camera_rows(held))
     kw = dict(steps=args.steps, downscale=args.downscale, backend=args.backend)
+    arms = [("one level", kw)]
+    if args.levels:
+        arms.append((f"levels {args.levels}", dict(levels=refine.parse_levels(args.levels), backend=args.backend)))
     print(f"{args.gaussians} Gaussians, {args.views} held-out {args.size} x {args.size} views (renderer raster), {args.steps} steps, downscale {args.downscale}, "
           f"backend {args.backend}")
-    for name, mult in (("perturbed x 1", 1.0), ("perturbed x 4", 4.0)):
+    for name, mult in (("perturbed x 1", 1.0), ("perturbed x 2", 2.0), ("perturbed x 4", 4.0)):
         off = torch.tensor([[mult * o * (1 if v % 2 == 0 else -1) for o in OFFSET] for v in range(args.views)], dtype=torch.float32)
         w2c = torch.eye(4).repeat(args.views, 1, 1)
         w2c[:, :3, :] = refine.compose(rows, off)[:, :12].reshape(-1, 3, 4)
         start = torch.linalg.inv(w2c)
-        out = refine.refine_poses(scene, images, start, K, **kw)
-        summarise(name, refine, gt, start, {k: v.cpu() for k, v in out.items()})
+        for arm, arm_kw in arms:
+            out = refine.refine_poses(scene, images, start, K, **arm_kw)
+            summarise(f"{name}, {arm}", refine, gt, start, {k: v.cpu() for k, v in out.items() if torch.is_tensor(v)})
         if mult == 1.0:
             step_split(refine, autograd, ops, scene, images, start, K, args.downscale)
     if args.iterations > 0:
@@ -114,13 +123,14 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.ckpt)), exist_ok=True)
         ts.train(idm, scene, train_cams, held, args.ckpt, args.iterations)
         results, *_ = pkg.test_pose_estimation(list(held), idm, *rays, ts.model_up_of(train_cams), verbose=False)
-        refine.refine_results(scene, list(held), results, **kw)
-        done = [r for r in results if "refined_c2w" in r]
-        start = torch.tensor([r["pred_c2w"] for r in done])
-        out = {"c2w": torch.tensor([r["refined_c2w"] for r in done]), "loss_start": torch.tensor([r["photometric_loss_before"] for r in done]),
-               "loss_best": torch.tensor([r["photometric_loss_after"] for r in done]), "best_step": torch.zeros(len(done), dtype=torch.int64)}
-        summarise(f"estimator ({args.iterations} training iterations; best step not kept by refine_results)", refine,
-                  torch.tensor([r["gt_c2w"] for r in done]), start, out)
+        for arm, arm_kw in arms:
+            refined = refine.refine_results(scene, list(held), [dict(r) for r in results], **arm_kw)
+            done = [r for r in refined if "refined_c2w" in r]
+            start = torch.tensor([r["pred_c2w"] for r in done])
+            out = {"c2w": torch.tensor([r["refined_c2w"] for r in done]), "loss_start": torch.tensor([r["photometric_loss_before"] for r in done]),
+                   "loss_best": torch.tensor([r["photometric_loss_after"] for r in done]), "best_step": torch.zeros(len(done), dtype=torch.int64)}
+            summarise(f"estimator ({args.iterations} training iterations; best step not kept by refine_results), {arm}", refine,
+                      torch.tensor([r["gt_c2w"] for r in done]), start, out)
 
 
 if __name__ == "__main__":
