@@ -85,6 +85,11 @@ SIGNATURES = {
     "sixdgs_fit_scene_steps": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i64, vp, i32, i32, i32, C.c_float, vp, vp, i32, i32, C.c_float, i32, i32,
                                      vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, i64] + [vp] * 5 + [vp] * 3
                                + [vp, sz, vp]),
+    "sixdgs_image_metrics_workspace_bytes": (sz, [i32, i32, i32]),
+    "sixdgs_image_metrics": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp, C.POINTER(Profile)]),
+    "sixdgs_evaluate_views_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
+    "sixdgs_evaluate_views": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, i32, i32, C.c_float, vp, vp, i32, i32, i32, i32, i64,
+                                    vp, vp, vp, vp, vp, sz, vp]),
     "sixdgs_packed_weights_floats": (sz, []),
     "sixdgs_pack_weights": (i32, [vp] * 13 + [C.POINTER(ScorerWeights), vp]),
     "sixdgs_ray_encode": (i32, [vp, vp, vp, i64, vp, vp]),

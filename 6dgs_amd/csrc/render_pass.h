@@ -1,4 +1,4 @@
-// render_pass.h -- the host side of one render-and-compare pass, shared by raster.hip, refine.hip and fit.hip: the scene and the
+// render_pass.h -- the host side of one render-and-compare pass, shared by raster.hip, refine.hip, fit.hip and metrics.hip: the scene and the
 // target as the entry points receive them, with their checks; the workspace every fused loop starts with; and the three calls of a
 // pass -- rasteriser, photometric loss, rasteriser's backward -- through their own entry points.  Internal: not part of the C ABI.
 #pragma once
@@ -27,6 +27,11 @@ struct Target {
   int is_u8, stride;
 };
 
+struct Image {
+  const float* data;     // fp32 [views,height,width,stride]: a render (stride 4, the fourth channel never read) or three plain channels
+  int stride;
+};
+
 // the numbers, for a render at sh_degree: asked before an entry point's `no views, nothing to do` ...
 inline bool scene_ok(const Scene& S, int sh_degree) {
   return S.scale_modifier > 0.f && S.scale_modifier < INFINITY && sh_degree >= 0 && sh_degree <= 3 &&
@@ -38,6 +43,10 @@ inline bool scene_present(const Scene& S) {
   return S.background && (S.n == 0 || (S.xyz && S.scale && S.rot && S.opacity && S.f_dc && (S.n_coef == 1 || S.f_rest)));
 }
 inline bool target_present(const Target& T) { return T.data && (T.is_u8 || aligned4(T.data)); }
+// the measured image and the input rule of the held-out-view metrics, in the same two halves
+inline bool image_ok(const Image& I) { return I.stride == 3 || I.stride == 4; }
+inline bool quantise_ok(int quantise) { return quantise == 0 || quantise == 1; }
+inline bool image_present(const Image& I) { return I.data && aligned4(I.data); }
 
 // What every loop's workspace starts with: the three entry points' own workspaces, the image, its gradient, the camera rows of the
 // views drawn, their losses and the instance count.  A loop's Layout derives from it and goes on with take().

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import autograd, ops
+from .evaluate import evaluate_prepared
 from .refine import ALPHA_MODES, BACKENDS, check_poses, posed_views
 from .scene import GaussianScene
 
@@ -206,7 +207,7 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
               spatial_lr_scale: float = 1.0, feature_lr: float = 2.5e-3, opacity_lr: float = 0.05, scaling_lr: float = 5e-3,
               rotation_lr: float = 1e-3, eps: float = 1e-15, lambda_dssim: float = 0.2, sh_degree_start=None, sh_up_every: int = 1000,
               opacity_reset_every: int = 0, reset_ceiling: float = 0.01, downscale: int = 1, alpha: str = "ignore",
-              background=(1.0, 1.0, 1.0), seed: int = 0, schedule=None, densify=None):
+              background=(1.0, 1.0, 1.0), seed: int = 0, schedule=None, densify=None, evaluate=None):
     """Fit `scene` (a GaussianScene on the GPU) to the posed `images` (uint8 [H,W,3|4] arrays or GPU tensors of one size) seen from
     c2w [V,4,4] with intrinsics K [3,3] or [V,3,3]: `steps` Adam steps, each on `batch` views, objective
     photometric_loss(raster_views(...)).sum() at 1 / downscale of the resolution.  Returns (new_scene, report): new_scene is a NEW
@@ -229,7 +230,15 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
     last one used).  opacity_reset_every=0 means never -- the default, because without densification a reset mostly harms; otherwise
     the opacity is reset to at most reset_ceiling after every opacity_reset_every-th iteration (only when "opacity" is among groups).
     schedule: int [steps, batch] view indices, overriding the default sampling without replacement (default_schedule, by seed).
-    alpha, downscale, background: refine.prepare_target's."""
+    alpha, downscale, background: refine.prepare_target's.
+
+    evaluate=None: nothing is measured -- today's loop, bit for bit.  Otherwise a dict {images, c2w, intrinsics, at, quantise=False,
+    chunk=8}: held-out views (evaluate.evaluate_views' arguments; downscale, alpha and background are the fit's) and `at`, step indices
+    in [0, steps].  An evaluation at s sees the scene BEFORE step s's update, at that step's SH degree; s = steps means the final
+    scene.  The reference's --test_iterations k is s = k - 1 in a fit without densification, because training_report runs before
+    the iteration's optimiser step.  report["evaluations"] is then a list, in ascending s, of {step, n (the Gaussians at that point),
+    l1, psnr, psnr_channels, ssim}: evaluate_views' means.  The fused backends cut their run at `at` (sixdgs_fit_scene_steps segments,
+    which compose to the one call bit for bit); evaluating never changes the fit."""
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {BACKENDS} (got {backend!r})")
     if alpha not in ALPHA_MODES:
@@ -291,6 +300,7 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
         degrees = np.minimum(sh_degree_start + (np.arange(steps) + 1) // sh_up_every, max_degree).astype(np.int32)
     plan = densify_plan(steps, densify, opacity_reset_every, "opacity" in groups)
     resets = plan["reset"]
+    watch = None if evaluate is None else _Evaluations(evaluate, steps, degrees, dev, downscale, alpha, background)
     views_t = torch.from_numpy(views.astype(np.int64)).to(dev)
     eps, lam = rates["eps"], float(lambda_dssim)
     if densify is not None:
@@ -299,8 +309,12 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
             opts["extent"] = cameras_extent(c2w)
         run = _fit_densify_fused if backend == "fused" else _fit_densify_torch
         params, history, status, rounds = run(params, cams, width, height, target, views_t, lrs, degrees, plan, opts, groups, lam, eps,
-                                              float(reset_ceiling), background)
+                                              float(reset_ceiling), background, watch)
         extra = {"rounds": rounds, "n_final": int(params["xyz"].shape[0])}
+    elif backend == "fused" and watch is not None:
+        extra = {}
+        history, status = _fit_fused_cut(params, cams, width, height, target, views, lrs, degrees, resets, groups, lam, eps,
+                                         float(reset_ceiling), background, watch)
     elif backend == "fused":
         extra = {}
         raw = ops.fit_scene_raw(params, cams, width, height, target, views=views, lrs=lrs, sh_degrees=degrees, resets=resets, groups=groups,
@@ -317,6 +331,8 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
         for s in range(steps):
             for group in opt.param_groups:
                 group["lr"] = float(np.float32(lrs[s][GROUPS.index(group["name"])]))
+            if watch is not None:
+                watch.before(s, params)
             idx = views_t[s]
             image = autograd.raster_views(*[params[k] for k in order], int(degrees[s]), cams[idx].contiguous(), width, height, background=background)
             loss = autograd.photometric_loss(image, target[idx].contiguous(), lam)
@@ -331,6 +347,9 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
                     state["exp_avg"].zero_()
                     state["exp_avg_sq"].zero_()
         params = {k: v.detach() for k, v in params.items()}
+    if watch is not None:
+        watch.before(steps, params)
+        extra["evaluations"] = watch.rows
     new = GaussianScene(max_degree)
     new.active_sh_degree = int(degrees[-1])
     for k, a in _SCENE_ATTR.items():
@@ -339,6 +358,77 @@ def fit_scene(scene, images, c2w, intrinsics, *, steps, batch: int = 1, backend:
 
 
 _ORDER = ops.SCENE_ARRAYS
+
+
+class _Evaluations:
+    """fit_scene's evaluate argument, checked and prepared once: before(s, params) measures the held-out views when s is in `at`."""
+
+    KEYS = {"images", "c2w", "intrinsics", "at", "quantise", "chunk"}
+
+    def __init__(self, spec, steps, degrees, dev, downscale, alpha, background):
+        if not isinstance(spec, dict) or not {"images", "c2w", "intrinsics", "at"} <= set(spec) <= self.KEYS:
+            raise ValueError(f"evaluate must be a dict with images, c2w, intrinsics, at and optionally quantise, chunk (got {spec!r:.80})")
+        at = sorted({_int_at_least(s, 0, "evaluate['at']") for s in spec["at"]})
+        if not at or at[-1] > steps:
+            raise ValueError(f"evaluate['at'] must name step indices in [0, {steps}]")
+        self.at, self.steps, self.degrees, self.background = at, steps, degrees, background
+        self.quantise, self.chunk = bool(spec.get("quantise", False)), _int_at_least(spec.get("chunk", 8), 1, "evaluate['chunk']")
+        c2w, K = check_poses(spec["images"], spec["c2w"], spec["intrinsics"], min_views=1)
+        self.target, self.cams, self.width, self.height = posed_views(spec["images"], c2w, K, dev, downscale, alpha, background)
+        self.rows = []
+
+    def cuts(self):
+        """The steps a fused run has to stop before."""
+        return [s for s in self.at if 0 < s < self.steps]
+
+    def restart(self):
+        self.rows = []
+
+    def before(self, s, params):
+        if s not in self.at:
+            return
+        with torch.no_grad():
+            r = evaluate_prepared([params[k].detach() for k in _ORDER], int(self.degrees[min(s, self.steps - 1)]), self.cams, self.width,
+                                  self.height, self.target, quantise=self.quantise, chunk=self.chunk, background=self.background)
+        self.rows.append({"step": int(s), "n": int(params["xyz"].shape[0]), "l1": float(r["mean_l1"]), "psnr": float(r["mean_psnr"]),
+                          "psnr_channels": float(r["mean_psnr_channels"]), "ssim": float(r["mean_ssim"])})
+
+
+def _fit_fused_cut(params, cams, width, height, target, views, lrs, degrees, resets, groups, lam, eps, ceiling, background, watch):
+    """fit_scene's fused backend without densification, cut before the steps `watch` measures at: one sixdgs_fit_scene_steps call per
+    segment from state zeroed here -- together the one sixdgs_fit_scene call, bit for bit.  status and the largest instance count are
+    read once at the end; when the capacity was too small the fit runs once more from the start, as ops.fit_scene_raw does.
+    params is updated in place -> (history, status)."""
+    steps, batch = views.shape
+    dev = cams.device
+    n = params["xyz"].shape[0]
+    start = {k: v.clone() for k, v in params.items()}
+    ends = watch.cuts() + [steps]
+    capacity = ops.raster_instances_estimate(n, batch)
+    for attempt in range(2):
+        state = ops.gaussian_adam_state(params)
+        state["instances_needed"] = torch.zeros(1, dtype=torch.int64, device=dev)
+        history = torch.empty(steps, batch, device=dev)
+        watch.restart()
+        first = 0
+        for end in ends:
+            watch.before(first, params)
+            seg = slice(first, end)
+            history[seg] = ops.fit_scene_steps_raw(params, cams, width, height, target, state, views=views[seg], lrs=lrs[seg],
+                                                   sh_degrees=degrees[seg], resets=resets[seg], first_adam_step=first, groups=groups,
+                                                   lambda_dssim=lam, eps=eps, reset_ceiling=ceiling, background=background,
+                                                   max_instances=capacity)
+            first = end
+        flags = torch.cat([state["status"].to(torch.int64), state["instances_needed"]]).cpu()
+        if not int(flags[0]) & ops.FIT_STATUS_CAPACITY:
+            break
+        if attempt == 1 or int(flags[1]) > ops.RASTER_MAX_INSTANCES:
+            raise RuntimeError(f"6dgs_amd: fit_scene still needs {int(flags[1])} tile instances after {attempt + 1} runs (limit 2^31 - 1): "
+                               "fit fewer views at once")
+        for k, v in start.items():
+            params[k].copy_(v)
+        capacity = ops._grown(int(flags[1]))
+    return history, state["status"]
 
 
 def _round_kw(opts, prune_big):
@@ -356,7 +446,7 @@ def _rounds_table(rows, dev):
     return torch.cat([head, counts[:, 1:], counts[:, :1]], dim=1)
 
 
-def _fit_densify_fused(start, cams, width, height, target, views_t, lrs, degrees, plan, opts, groups, lam, eps, ceiling, background):
+def _fit_densify_fused(start, cams, width, height, target, views_t, lrs, degrees, plan, opts, groups, lam, eps, ceiling, background, watch=None):
     """fit_scene's fused backend with densification: segments of sixdgs_fit_scene_steps that end at the rounds' iterations, one
     sixdgs_densify per round into buffers of 2 n rows (so a round never retries) and one 8-byte read of n_out behind it.  status and the
     largest instance count are read once at the end; when the capacity was too small the whole fit runs once more, from the start,
@@ -367,6 +457,8 @@ def _fit_densify_fused(start, cams, width, height, target, views_t, lrs, degrees
     ends = [int(s) + 1 for s in np.nonzero(plan["round"])[0]]
     if not ends or ends[-1] != steps:
         ends.append(steps)
+    if watch is not None:           # the evaluations' cut points; a segment that ends at one of them alone is no round's
+        ends = sorted(set(ends) | set(watch.cuts()))
     floor = 0
     for attempt in range(2):
         params = {k: v.clone() for k, v in start.items()}
@@ -376,7 +468,11 @@ def _fit_densify_fused(start, cams, width, height, target, views_t, lrs, degrees
         stats = ops.densify_stats_state(n, dev)
         history = torch.empty(steps, batch, device=dev)
         rows, first, updates_made = [], 0, 0
+        if watch is not None:
+            watch.restart()
         for end in ends:
+            if watch is not None:
+                watch.before(first, params)
             seg = slice(first, end)
             is_round = bool(plan["round"][end - 1])
             seg_resets = plan["reset"][seg].copy()
@@ -410,7 +506,7 @@ def _fit_densify_fused(start, cams, width, height, target, views_t, lrs, degrees
     return params, history, state["status"], _rounds_table(rows, dev)
 
 
-def _fit_densify_torch(start, cams, width, height, target, views_t, lrs, degrees, plan, opts, groups, lam, eps, ceiling, background):
+def _fit_densify_torch(start, cams, width, height, target, views_t, lrs, degrees, plan, opts, groups, lam, eps, ceiling, background, watch=None):
     """fit_scene's torch backend with densification, the reference arm: the same schedule with torch.optim.Adam; the render pass goes
     through the raw ops so that ops.densify_stats can follow the backward; the round is densify_torch, with the optimiser-state surgery
     of the reference's cat_tensors_to_optimizer / _prune_optimizer."""
@@ -424,6 +520,8 @@ def _fit_densify_torch(start, cams, width, height, target, views_t, lrs, degrees
     rows = []
     want = tuple(k for k in _ORDER if k in groups)
     for s in range(steps):
+        if watch is not None:
+            watch.before(s, params)
         for group in opt.param_groups:
             group["lr"] = float(np.float32(lrs[s][GROUPS.index(group["name"])]))
         idx = views_t[s]

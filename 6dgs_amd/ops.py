@@ -563,6 +563,111 @@ def photometric_loss(image: torch.Tensor, target: torch.Tensor, *, lambda_dssim:
     return out[0] if len(out) == 1 else tuple(out)
 
 
+METRICS = ("l1", "ssim", "mse", "mse_r", "mse_g", "mse_b")      # the columns of sixdgs_image_metrics' rows
+EVALUATE_STATUS_CAPACITY = 2
+
+
+def image_metrics_workspace_bytes(views: int, width: int, height: int) -> int:
+    return int(_lib.load().sixdgs_image_metrics_workspace_bytes(int(views), int(width), int(height)))
+
+
+def _quantise(quantise) -> int:
+    if not isinstance(quantise, (bool, int)) or int(quantise) not in (0, 1):
+        raise ValueError(f"quantise must be a flag (got {quantise!r})")
+    return int(quantise)
+
+
+@_on_device
+def image_metrics(image: torch.Tensor, target: torch.Tensor, *, quantise, want_render: bool = False, workspace: Optional[torch.Tensor] = None,
+                  profile: Optional[Profile] = None):
+    """L1, SSIM and the squared error per view (sixdgs_image_metrics in include/sixdgs.h defines them operation by operation).  image,
+    target: photometric_loss's.  quantise False clamps the float inputs to [0, 1]; True passes them through the 8-bit round trip of a
+    saved PNG.  Returns metrics fp32 [V,6] in the order of METRICS, and with want_render (metrics, render_u8 uint8 [V,H,W,3]): the
+    image's bytes by the 8-bit rule."""
+    q = _quantise(quantise)
+    if not torch.is_tensor(image) or image.dim() != 4 or image.shape[3] not in (3, 4):
+        raise ValueError(f"image must be a [views,height,width,3|4] tensor (got {tuple(image.shape) if torch.is_tensor(image) else type(image).__name__})")
+    if image.dtype != torch.float32:
+        raise ValueError(f"image must be float32 (got {image.dtype})")
+    if not image.is_contiguous():
+        raise ValueError("image must be contiguous")
+    views, height, width, stride = image.shape
+    if width < 1 or height < 1:
+        raise ValueError(f"width and height must be positive (got {width} x {height})")
+    target, target_is_u8, target_stride = _target_args(target, views, height, width)
+    image = image.detach()
+    _need_gpu(image, target, workspace)
+    lib = _lib.load()
+    dev = image.device
+    need = lib.sixdgs_image_metrics_workspace_bytes(views, width, height)
+    if need == 0 and views > 0:
+        raise ValueError(f"sizes outside the metrics' limits (views {views}, {width} x {height})")
+    ws, ws_bytes = _workspace(workspace, need, dev)
+    metrics = torch.empty(views, len(METRICS), dtype=torch.float32, device=dev)
+    render = torch.empty(views, height, width, 3, dtype=torch.uint8, device=dev) if want_render else None
+    check(lib.sixdgs_image_metrics(_p(image), stride, _p(target), target_is_u8, target_stride, views, width, height, q, _p(metrics), _p(render),
+                                   _p(ws), ws_bytes, _stream(), profile),
+          "image_metrics")
+    return (metrics, render) if want_render else metrics
+
+
+def evaluate_views_workspace_bytes(n: int, chunk: int, width: int, height: int, max_instances: int) -> int:
+    return int(_lib.load().sixdgs_evaluate_views_workspace_bytes(int(n), int(chunk), int(width), int(height), int(max_instances)))
+
+
+@_on_device
+def evaluate_views_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: torch.Tensor, width: int, height: int,
+                       target: torch.Tensor, *, quantise, chunk: int = 8, want_render: bool = False, scale_modifier: float = 1.0,
+                       background=(1.0, 1.0, 1.0), scale_is_log: bool = True, opacity_is_logit: bool = True,
+                       max_instances: Optional[int] = None, retry: bool = True, workspace: Optional[torch.Tensor] = None) -> dict:
+    """Render the views cams [V,16] and measure them against target as ONE library call (sixdgs_evaluate_views in include/sixdgs.h):
+    chunks of `chunk` views, each rasterised and measured on the device, nothing read back in between.  max_instances is the capacity
+    of one chunk.  Returns a dict: metrics fp32 [V,6] (METRICS' order), status (int32 [1]; bit 1: a chunk did not fit the capacity and
+    its rows are NaN), render (uint8 [V,height,width,3], with want_render), instances_needed and max_instances (ints).  The call
+    reads status and instances_needed once at the end and -- with retry -- on bit 1 runs once more with the needed capacity."""
+    q = _quantise(quantise)
+    if isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError(f"chunk must be a positive integer (got {chunk!r})")
+    cams, width, height = _view_args(cams, width, height, background, scale_modifier)
+    scene, n, n_coef = _scene(xyz, scale, rot, opacity, f_dc, f_rest)
+    views = cams.shape[0]
+    chunk = max(min(int(chunk), views), 1)
+    capacity = _capacity(max_instances, n, chunk)
+    target, target_is_u8, target_stride = _target_args(target, views, height, width)
+    _need_gpu(*scene, cams, target, workspace)
+    lib = _lib.load()
+    dev = scene[0].device
+    bg = _background(background, dev)
+    out = {"metrics": torch.empty(views, len(METRICS), dtype=torch.float32, device=dev), "status": torch.zeros(1, dtype=torch.int32, device=dev)}
+    if want_render:
+        out["render"] = torch.empty(views, height, width, 3, dtype=torch.uint8, device=dev)
+    needed_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    needed = 0
+    for attempt in range(2):
+        need = lib.sixdgs_evaluate_views_workspace_bytes(n, chunk, width, height, capacity)
+        if need == 0:
+            raise ValueError(f"sizes outside the rasteriser's limits (n {n}, chunk {chunk}, {width} x {height}, instances {capacity})")
+        ws, ws_bytes = _workspace(workspace, need, dev)
+        check(lib.sixdgs_evaluate_views(*_scene_args(scene, n_coef, scale_is_log, opacity_is_logit), int(sh_degree), int(n_coef), n, _p(cams),
+                                        views, width, height, float(scale_modifier), _p(bg), _p(target), target_is_u8, target_stride, q, chunk,
+                                        capacity, _p(out["metrics"]), _p(out.get("render")), _p(out["status"]), _p(needed_t), _p(ws), ws_bytes,
+                                        _stream()),
+              "evaluate_views")
+        if views == 0:
+            break
+        # the one host read of the call: the status word and the largest instance count seen
+        flags = torch.cat([out["status"].to(torch.int64), needed_t]).cpu()
+        needed = int(flags[1])
+        if not retry or not int(flags[0]) & EVALUATE_STATUS_CAPACITY:
+            break
+        if attempt == 1 or needed > RASTER_MAX_INSTANCES:
+            raise RuntimeError(f"6dgs_amd: evaluate_views needs {needed} tile instances per chunk (limit 2^31 - 1): use a smaller chunk")
+        capacity = needed
+    out["instances_needed"] = needed
+    out["max_instances"] = capacity
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # pose refinement below the C ABI
 # ---------------------------------------------------------------------------------------------

@@ -682,6 +682,62 @@ size_t sixdgs_knn_workspace_bytes(int64_t n);
 int sixdgs_knn_mean_dist2(int64_t n, const float* xyz /*[n][3]*/, float* mean_d2 /*[n]*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Held-out-view metrics (additive in ABI 10): per view L1, SSIM and the squared error, whole and per channel, between an image a and
+ * a target b -- what the reference's evaluation forms from them (metrics.py:69-89 after the 8-bit PNG round trip of render.py:25-40;
+ * train.py:233-289's training_report after a clamp to [0, 1]).  PSNR is not formed here: it is 10 log10(1 / mse), the caller's
+ * logarithm, so no transcendental enters the definition.  All fp32 arithmetic without contraction into fused multiply-adds.
+ *
+ * INPUTS are sixdgs_photometric_loss's: image fp32 [views][height][width][image_stride], image_stride 3 or 4 (the fourth channel is
+ * never read); target fp32 with target_stride 3 or 4, or uint8 [views][height][width][3] (target_is_u8 == 1, target_stride 3).
+ * INPUT RULE, per value x of an fp32 input (the image, and a float target):
+ *   quantise == 0 (training_report's clamp):  value = fminf(fmaxf(x, 0), 1); NaN counts as 0;
+ *   quantise == 1 (the PNG round trip):       u = (int) truncf(fminf(fmaxf(x * 255.0f + 0.5f, 0), 255)), value = float(u) / 255.0f;
+ *     NaN counts as 0.  This is torchvision's save_image -- mul(255).add_(0.5).clamp_(0, 255).to(uint8) -- followed by to_tensor's
+ *     division.  It is NOT sixdgs_raster_views' image_u8 rule round(255 clamp(., 0, 1)): the two differ at about one fp32 value in
+ *     10^5 and at half of the exact half points (k + 0.5) / 255, so the bytes are formed here and image_u8 is not read.
+ * A uint8 target's value is float(u) / 255.0f in both modes; the 8-bit rule maps each of the 256 such values to its own byte.
+ * OUTPUTS.  metrics [views][6] = (l1, ssim, mse, mse_r, mse_g, mse_b), WRITTEN, NOT ACCUMULATED.  With a, b the values after the rule:
+ *   ssim: steps 3 - 7 of sixdgs_photometric_loss on a, b -- the same window, zero padding, tile tree and order of tiles;
+ *   quantise == 0:  l1 by step 7's tree; with d = a - b, s_c = the sum of d d over channel c's pixels in the same tree (per pixel one
+ *     term; tile tree; tiles in row-major order), mse_c = s_c / float(height width), mse = ((s_r + s_g) + s_b) / float(3 height width);
+ *   quantise == 1:  both sides are bytes ua, ub: S1 = sum |ua - ub| over all channels and S2_c = sum (ua - ub)^2 per channel are exact
+ *     integers (32 bits per tile, 64 per view), and one fp64 division per output rounds once:
+ *     l1 = float(double(S1) / (255.0 (3 height width))), mse_c = float(double(S2_c) / (65025.0 (height width))),
+ *     mse = float(double(S2_r + S2_g + S2_b) / (65025.0 (3 height width))) -- reproducible to the bit on any host.
+ *   render_u8 [views][height][width][3] (may be NULL): the image's bytes by the quantise == 1 rule, whatever quantise is -- what a caller
+ *     saves as PNG --, written in the same pass.
+ * SAME INPUT, SAME BYTES: no floating-point atomics.  VIEWS DO NOT MIX: metrics[v] and render_u8[v] are the same bits whether view v is
+ * passed alone or in a batch.  Nothing is read or written outside the arrays as declared.  image, a float target and metrics are 4-byte
+ * aligned, ws 256-byte.  Limits are sixdgs_photometric_loss's: 1 <= width, height <= 16384, views <= 65535, views gx gy < 2^31.
+ * Argument errors: SIXDGS_E_BADARG; too small a workspace: SIXDGS_E_WORKSPACE; both without touching a GPU.  views == 0 returns 0.
+ * sixdgs_image_metrics_workspace_bytes is answered without a GPU and is 0 outside the limits: 20 B per tile and view.  One 256-thread
+ * workgroup per 16 x 16 tile and view, then one per view.  prof (may be NULL) receives one slot per stage: moments, sums.
+ *
+ * sixdgs_evaluate_views renders and measures many views as one call.  Scene arrays, flags, sh_degree, scale_modifier and background
+ * (device [3]) as sixdgs_raster_views takes them; cams [views][16]; the target in the three forms above, views images of width x height.
+ * It zeroes status[0] and instances_needed[0], then for each chunk of up to `chunk` (>= 1) consecutive views enqueues on `stream`,
+ * through the entry points as they are: sixdgs_raster_views of the chunk's rows (float image only; the count stays on the device),
+ * sixdgs_image_metrics into the chunk's rows of metrics (and of render_u8, when given), and a record: instances_needed[0] =
+ * max(instances_needed[0], count); if count > max_instances, bit 1 of status[0] is set and the chunk's metrics rows are NaN (its
+ * render_u8 rows are unspecified); other chunks are unaffected.  No host synchronisation, no device-to-host copy, no allocation; the
+ * library stays stateless; when it returns, the work is enqueued.  metrics[v] is the same bits for every chunk and whether view v is
+ * evaluated alone or with others, given a capacity that fits.  Limits and errors are the parts'; views == 0 returns 0.
+ * sixdgs_evaluate_views_workspace_bytes is answered without a GPU and is 0 outside the limits: the two parts' workspaces at `chunk`
+ * views, one float image of chunk x height x width x 4 and the count, each piece rounded up to 256 B. */
+size_t sixdgs_image_metrics_workspace_bytes(int views, int width, int height);
+int sixdgs_image_metrics(const float* image /*[views][height][width][image_stride]*/, int image_stride /*3 or 4*/, const void* target,
+                         int target_is_u8, int target_stride /*3 or 4; 3 with uint8*/, int views, int width, int height, int quantise,
+                         float* metrics /*[views][6]*/, uint8_t* render_u8 /*[views][height][width][3] or NULL*/, void* ws, size_t ws_bytes,
+                         sixdgs_stream_t stream, sixdgs_profile* prof);
+size_t sixdgs_evaluate_views_workspace_bytes(int64_t n, int chunk, int width, int height, int64_t max_instances);
+int sixdgs_evaluate_views(const float* xyz, const float* scale, int scale_is_log, const float* rot, const float* opacity, int opacity_is_logit,
+                          const float* f_dc, const float* f_rest, int sh_degree, int n_coef, int64_t n, const float* cams /*[views][16]*/,
+                          int views, int width, int height, float scale_modifier, const float* background /*[3] device*/, const void* target,
+                          int target_is_u8, int target_stride, int quantise, int chunk, int64_t max_instances, float* metrics /*[views][6]*/,
+                          uint8_t* render_u8 /*or NULL*/, int32_t* status /*[1]*/, int64_t* instances_needed /*[1]*/, void* ws,
+                          size_t ws_bytes, sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scorer, scene side (once per scene): ray MLP + k_proj -> key cache
  * replaces RayPreprocessor.forward (ray_preprocessor.py:36-46) + k_proj (our_multihead_attention.py:74)
  * ------------------------------------------------------------------------------------------- */

@@ -71,16 +71,13 @@ def densify_demo(pkg, fit, scene, images, c2w, K, args):
               f"{float(h[-tail:].mean()):.5f}; status {int(rep['status'])}; rounds (iteration, n, clones, splits, pruned, n after): {rounds}")
 
 
-def psnr(render, scene, held):
-    """Mean over the views of 10 log10(1 / MSE) between the scene's rasterised views and the targets, on [0, 1]."""
-    out = render.render_views(scene, held, renderer="raster")
-    diff = [(np.asarray(a.image[..., :3], np.float64) - np.asarray(b.image[..., :3], np.float64)) / 255.0 for a, b in zip(out, held)]
-    mse = [float((d * d).mean()) for d in diff]
-    return float(np.mean([10.0 * np.log10(1.0 / max(m, 1e-12)) for m in mse]))
+def psnr(pkg, scene, images, c2w, K):
+    """Mean PSNR of the scene's rasterised views against the images: evaluate_views' metrics.py definition, nothing read back but the
+    per-view numbers."""
+    return float(pkg.evaluate_views(scene, images, c2w, K)["mean_psnr"])
 
 
 def from_points_demo(pkg, fit, scene, held, images, c2w, K, args):
-    render = importlib.import_module("6dgs_amd.render")
     n = min(args.from_points, len(scene))
     idx = torch.randperm(len(scene), generator=torch.Generator().manual_seed(args.seed))[:n].sort().values.to(scene._xyz.device)
     colors = (scene._features_dc[idx, 0, :] * 0.28209479177387814 + 0.5).clamp(0.0, 1.0)
@@ -88,13 +85,13 @@ def from_points_demo(pkg, fit, scene, held, images, c2w, K, args):
     opts = dict(from_iter=args.from_iter, until_iter=args.until_iter, interval=args.interval, grad_threshold=args.grad)
     sigma = torch.exp(start._scaling[:, 0])
     print(f"{n} of {len(scene)} centres -> from_points: scale quantiles 10 / 50 / 90 % {', '.join(f'{float(q):.4f}' for q in sigma.quantile(torch.tensor([0.1, 0.5, 0.9], device=sigma.device)))}; "
-          f"{args.views} views of {args.size} x {args.size}, {args.steps} steps; densify {opts}; PSNR before {psnr(render, start, held):.2f} dB")
+          f"{args.views} views of {args.size} x {args.size}, {args.steps} steps; densify {opts}; PSNR before {psnr(pkg, start, images, c2w, K):.2f} dB")
     tail = max(min(args.views // args.batch, args.steps), 1)
     for backend in ("fused", "torch"):
         new, rep = fit.fit_scene(start, images, c2w, K, steps=args.steps, batch=args.batch, backend=backend, densify=opts, sh_degree_start=0)
         h = rep["loss_history"]
         print(f"{backend}: n {len(start)} -> {len(new)}; loss, mean of the first {tail} steps {float(h[:tail].mean()):.5f}, of the last {tail} "
-              f"{float(h[-tail:].mean()):.5f}; PSNR after {psnr(render, new, held):.2f} dB; status {int(rep['status'])}; rounds {rep['rounds'].tolist()}")
+              f"{float(h[-tail:].mean()):.5f}; PSNR after {psnr(pkg, new, images, c2w, K):.2f} dB; status {int(rep['status'])}; rounds {rep['rounds'].tolist()}")
 
 
 def rms(a, b):
