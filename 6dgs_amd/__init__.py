@@ -29,7 +29,9 @@ from .autograd import photometric_loss, raster_views  # noqa: F401
 from .refine import refine_poses, refine_results  # noqa: F401
 from .evaluate import evaluate_views  # noqa: F401
 from .fit import fit_scene  # noqa: F401
+from .contribution import prune_by_contribution, scene_contribution  # noqa: F401
 
 __all__ = ["GaussianModel", "GaussianScene", "CameraInfo", "generate_all_possible_rays", "IdentificationModule",
            "test_pose_estimation", "DistanceBasedScoreLoss", "train_id_module", "render_views", "raster_views", "photometric_loss",
-           "refine_poses", "refine_results", "fit_scene", "evaluate_views"]
+           "refine_poses", "refine_results", "fit_scene", "evaluate_views", "scene_contribution",
+           "prune_by_contribution"]

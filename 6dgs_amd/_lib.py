@@ -59,6 +59,11 @@ SIGNATURES = {
     "sixdgs_raster_views_backward_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
     "sixdgs_raster_views_backward": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, i32, i32, C.c_float, vp, vp, i64, vp, sz,
                                            vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Profile)]),
+    "sixdgs_raster_contrib_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
+    "sixdgs_raster_contrib": (i32, [i64, i32, i32, i32, i64, vp, sz] + [vp] * 7 + [vp, sz, vp, C.POINTER(Profile)]),
+    "sixdgs_scene_contrib_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
+    "sixdgs_scene_contrib": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, i32, i32, C.c_float, i32, i64] + [vp] * 7
+                             + [vp, vp, vp, sz, vp]),
     "sixdgs_photometric_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "sixdgs_photometric_loss": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Profile)]),
     "sixdgs_pose_compose": (i32, [vp, vp, i32, vp, vp]),

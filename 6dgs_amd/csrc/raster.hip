@@ -11,7 +11,8 @@
 //   blend    k_raster_blend    one workgroup of 256 lanes per tile, one pixel per lane; rounds of 256 instances staged in LDS
 //
 // The backward (sixdgs_raster_views_backward: k_raster_blend_bwd, k_raster_project_bwd, k_raster_cams_bwd) is further down; it reads this
-// workspace and sorts nothing again.
+// workspace and sorts nothing again.  So does the contribution pass behind it (sixdgs_raster_contrib: k_raster_contrib_walk,
+// k_raster_contrib_gather), which repeats the blend's walk and keeps alpha T per (view, Gaussian) instead of a colour.
 //
 // When the scene needs more than max_instances pairs, emit / ranges / blend read the total on the device and return; nothing is
 // written past a buffer, `instances` still receives the needed number.  No kernel here uses scratch or a global atomic, and every
@@ -871,6 +872,154 @@ BwdLayout bwd_layout(int64_t n, int views, int64_t max_instances) {
   return L;
 }
 
+// ---- contributions (include/sixdgs.h, sixdgs_raster_contrib) -----------------------------------------------------------------------
+//   walk    k_raster_contrib_walk    one workgroup per tile and view, one pixel per lane: the forward's walk, operation by operation, in
+//           rounds of 256 staged in LDS.  All lanes stay in step per list entry; a lane that skipped or has stopped counts 0.f / 0.  Where
+//           the wave's ballot says some lane added or stopped, the wave reduces w = alpha T (sum and max by xor 32 .. 1) and counts the
+//           two ballots; lane 0 leaves the partial in LDS.  After the round thread tid adds waves 0 .. 3 in order into instance tid's OWN
+//           slot offs[vi] + (ty - y0)(x1 - x0) + (tx - x0): every slot is written exactly once, no memset, no atomic
+//   gather  k_raster_contrib_gather  one lane per Gaussian, views in ascending order, slots in order; accumulators in registers, one
+//           read-modify-write per output
+// Reads the forward's workspace, writes only its own slots and the outputs.
+struct ContribWalkArgs {
+  Records r;
+  const int64_t* total;
+  const int2* ranges;
+  const uint32_t *vals0, *vals1;
+  const uint32_t* which;
+  uint4* slots;                 // per instance: bits of the sum of w, bits of the largest w, pixels that added, pixels it stopped
+  int64_t n, max_instances;
+  int width, height, gx, gy;
+};
+
+__global__ __launch_bounds__(256) void k_raster_contrib_walk(ContribWalkArgs B) {
+  __shared__ float4 s_co[256];
+  __shared__ float2 s_uv[256];
+  __shared__ uint4 s_part[256 * 4];            // [entry j][wave]
+  if (*B.total > B.max_instances) return;
+  const int tid = threadIdx.x, view = blockIdx.z, wave = tid >> 6, lane = tid & 63;
+  const int2 rg = B.ranges[((int64_t)view * B.gy + blockIdx.y) * B.gx + blockIdx.x];
+  if (rg.y <= rg.x) return;
+  const uint32_t* __restrict__ vals = *B.which ? B.vals1 : B.vals0;
+  const int x = blockIdx.x * kTile + (tid & 15), y = blockIdx.y * kTile + (tid >> 4);
+  const bool inside = x < B.width && y < B.height;
+  const float xf = (float)x, yf = (float)y;
+  const int64_t rec0 = (int64_t)view * B.n;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);          // (0.f, 0.f, 0, 0)
+  bool done = !inside;
+  float T = 1.f;
+  for (int base = rg.x; base < rg.y; base += 256) {
+    const bool over = __syncthreads_and(done);            // (also: everybody has left the previous round's LDS)
+    const int m = min(256, rg.y - base);
+    int64_t slot = -1, rec = 0;
+    if (tid < m) {
+      rec = rec0 + vals[base + tid];
+      const ushort4 rc = B.r.rect[rec];
+      slot = B.r.offs[rec] + (int64_t)((int)blockIdx.y - (int)rc.y) * ((int)rc.z - (int)rc.x) + ((int)blockIdx.x - (int)rc.x);
+      if (slot < 0 || slot >= B.max_instances) slot = -1;          // (cannot happen with the workspace of a completed forward)
+    }
+    if (over) {                   // every pixel has stopped: zeros
+      if (slot >= 0) B.slots[slot] = zero;
+      continue;
+    }
+    if (tid < m) {
+      s_co[tid] = B.r.co[rec];
+      s_uv[tid] = B.r.uv[rec];
+    }
+#pragma unroll
+    for (int w = 0; w < 4; ++w) s_part[tid * 4 + w] = zero;
+    __syncthreads();
+    for (int j = 0; j < m; ++j) {
+      if (__ballot(!done) == 0) break;          // (uniform in the wave) its partials of the rest stay zero
+      float w = 0.f;
+      bool add = false, stop = false;
+      if (!done) {
+        const float2 uv = s_uv[j];
+        const float4 co = s_co[j];
+        const float dx = (uv.x - xf) - 0.5f, dy = (uv.y - yf) - 0.5f;
+        const float power = -0.5f * ((co.x * dx) * dx + (co.z * dy) * dy) - (co.y * dx) * dy;
+        if (!(power > 0.f)) {
+          const float alpha = fminf(0.99f, co.w * expf(power));
+          if (!(alpha < 1.f / 255.f)) {
+            const float Tn = T * (1.f - alpha);
+            if (Tn < 1e-4f) {
+              done = true;
+              stop = true;
+            } else {
+              w = alpha * T;
+              add = true;
+              T = Tn;
+            }
+          }
+        }
+      }
+      const u64 adds = __ballot(add), stops = __ballot(stop);
+      if ((adds | stops) != 0) {      // (uniform in the wave)
+        const float sum = sdg_wave_sum(w), peak = sdg_wave_max(w);
+        if (lane == 0) s_part[j * 4 + wave] = make_uint4(__float_as_uint(sum), __float_as_uint(peak), (uint32_t)__popcll(adds), (uint32_t)__popcll(stops));
+      }
+    }
+    __syncthreads();
+    if (slot >= 0) {
+      const uint4 p0 = s_part[tid * 4], p1 = s_part[tid * 4 + 1], p2 = s_part[tid * 4 + 2], p3 = s_part[tid * 4 + 3];
+      const float sum = ((__uint_as_float(p0.x) + __uint_as_float(p1.x)) + __uint_as_float(p2.x)) + __uint_as_float(p3.x);
+      const float peak = fmaxf(fmaxf(__uint_as_float(p0.y), __uint_as_float(p1.y)), fmaxf(__uint_as_float(p2.y), __uint_as_float(p3.y)));
+      B.slots[slot] = make_uint4(__float_as_uint(sum), __float_as_uint(peak), ((p0.z + p1.z) + p2.z) + p3.z, ((p0.w + p1.w) + p2.w) + p3.w);
+    }
+  }
+}
+
+struct ContribGatherArgs {
+  const int64_t *cnt, *offs;
+  const uint4* slots;
+  float *weight, *peak;
+  int64_t *pixels, *stops;
+  int32_t* seen;
+  float* view_weight;
+  int32_t* view_pixels;
+  int64_t n, max_instances;
+  int views;
+};
+
+__global__ __launch_bounds__(256) void k_raster_contrib_gather(ContribGatherArgs A) {
+  if (A.offs[(int64_t)A.views * A.n] > A.max_instances) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= A.n) return;
+  float weight = A.weight ? A.weight[i] : 0.f, peak = A.peak ? A.peak[i] : 0.f;
+  int64_t pixels = A.pixels ? A.pixels[i] : 0, stops = A.stops ? A.stops[i] : 0;
+  int32_t seen = A.seen ? A.seen[i] : 0;
+  for (int view = 0; view < A.views; ++view) {
+    const int64_t vi = (int64_t)view * A.n + i;
+    const int64_t cnt = A.cnt[vi];
+    float w = 0.f, pk = 0.f;
+    int32_t px = 0, st = 0;
+    if (cnt > 0) {
+      const uint4* __restrict__ sl = A.slots + A.offs[vi];
+      for (int64_t t = 0; t < cnt; ++t) {
+        const uint4 s = sl[t];
+        w += __uint_as_float(s.x);
+        pk = fmaxf(pk, __uint_as_float(s.y));
+        px += (int32_t)s.z;
+        st += (int32_t)s.w;
+      }
+    }
+    weight += w;
+    peak = fmaxf(peak, pk);
+    pixels += px;
+    stops += st;
+    seen += px > 0;
+    if (A.view_weight) A.view_weight[vi] = w;
+    if (A.view_pixels) A.view_pixels[vi] = px;
+  }
+  if (A.weight) A.weight[i] = weight;
+  if (A.peak) A.peak[i] = peak;
+  if (A.pixels) A.pixels[i] = pixels;
+  if (A.stops) A.stops[i] = stops;
+  if (A.seen) A.seen[i] = seen;
+}
+
+inline size_t contrib_bytes(int64_t max_instances) { return sdg_align((size_t)max_instances * sizeof(uint4)); }
+
 }  // namespace
 
 extern "C" {
@@ -1049,6 +1198,46 @@ int sixdgs_densify_stats(int64_t n, int views, int width, int height, int64_t ma
                  denom, max_radii, grad2d, status, n, max_instances, views, 0.5f * (float)width, 0.5f * (float)height};
   hipLaunchKernelGGL(k_densify_stats, dim3((unsigned)sdg_cdiv(n, 256)), dim3(256), 0, sdg_stream(stream), A);
   SDG_LAUNCH_OK();
+  return 0;
+}
+
+size_t sixdgs_raster_contrib_workspace_bytes(int64_t n, int views, int width, int height, int64_t max_instances) {
+  if (!sizes_ok(n, views, width, height, max_instances)) return 0;
+  return contrib_bytes(max_instances);
+}
+
+int sixdgs_raster_contrib(int64_t n, int views, int width, int height, int64_t max_instances, const void* fwd_ws, size_t fwd_ws_bytes,
+                          float* weight, float* peak, int64_t* pixels, int64_t* stops, int32_t* seen, float* view_weight,
+                          int32_t* view_pixels, void* ws, size_t ws_bytes, sixdgs_stream_t stream, sixdgs_profile* prof) {
+  SDG_CHECK_ARG(sizes_ok(n, views, width, height, max_instances));
+  if (views == 0 || n == 0) return 0;
+  SDG_CHECK_ARG(fwd_ws);
+  SDG_CHECK_ARG(rp::aligned4(weight) && rp::aligned4(peak) && ((uintptr_t)pixels & 7) == 0 && ((uintptr_t)stops & 7) == 0 && rp::aligned4(seen) &&
+                rp::aligned4(view_weight) && rp::aligned4(view_pixels));
+  const Layout F = layout(n, views, width, height, max_instances);
+  if (fwd_ws_bytes < F.total || ws_bytes < contrib_bytes(max_instances)) return SIXDGS_E_WORKSPACE;
+  SDG_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0 && ((uintptr_t)fwd_ws & 255) == 0);
+  if (!(weight || peak || pixels || stops || seen || view_weight || view_pixels)) return 0;
+  hipStream_t s = sdg_stream(stream);
+  const char* f = (const char*)fwd_ws;
+  const int gx = (int)sdg_cdiv(width, kTile), gy = (int)sdg_cdiv(height, kTile);
+  const int64_t vn = (int64_t)views * n;
+  Records r = {(float4*)(f + F.co), (float2*)(f + F.uv), (float*)(f + F.rgb), (uint32_t*)(f + F.depth), (ushort4*)(f + F.rect),
+               (int64_t*)(f + F.cnt), (int64_t*)(f + F.offs)};
+  uint4* slots = (uint4*)ws;
+  {
+    SdgProfileScope t(prof, s, 0, 0);
+    ContribWalkArgs B = {r, r.offs + vn, (const int2*)(f + F.ranges), (const uint32_t*)(f + F.vals0), (const uint32_t*)(f + F.vals1),
+                         (const uint32_t*)(f + F.scan_tmp), slots, n, max_instances, width, height, gx, gy};
+    hipLaunchKernelGGL(k_raster_contrib_walk, dim3((unsigned)gx, (unsigned)gy, (unsigned)views), dim3(256), 0, s, B);
+    SDG_LAUNCH_OK();
+  }
+  {
+    SdgProfileScope t(prof, s, 0, 0);
+    ContribGatherArgs A = {r.cnt, r.offs, slots, weight, peak, pixels, stops, seen, view_weight, view_pixels, n, max_instances, views};
+    hipLaunchKernelGGL(k_raster_contrib_gather, dim3((unsigned)sdg_cdiv(n, 256)), dim3(256), 0, s, A);
+    SDG_LAUNCH_OK();
+  }
   return 0;
 }
 

@@ -516,6 +516,121 @@ def raster_views_backward(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int
     return tuple(out.get(k) for k in RASTER_GRADIENTS)
 
 
+# the accumulators of sixdgs_raster_contrib, in the order its entry points take them
+CONTRIB = (("weight", torch.float32), ("peak", torch.float32), ("pixels", torch.int64), ("stops", torch.int64), ("seen", torch.int32))
+CONTRIB_VIEWS = (("view_weight", torch.float32), ("view_pixels", torch.int32))
+CONTRIB_STATUS_CAPACITY = 2
+
+
+def contrib_state(n: int, device) -> dict:
+    """The accumulators of raster_contrib, zeroed: weight, peak float32 [n], pixels, stops int64 [n], seen int32 [n]."""
+    return {k: torch.zeros(int(n), dtype=dt, device=device) for k, dt in CONTRIB}
+
+
+def _check_contrib(out, n):
+    if not isinstance(out, dict) or any(k not in dict(CONTRIB) for k in out):
+        raise ValueError(f"out must be a dict with some of the keys {tuple(k for k, _ in CONTRIB)} (ops.contrib_state makes it)")
+    for k, dt in CONTRIB:
+        t = out.get(k)
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous()):
+            raise ValueError(f"out[{k!r}] must be a contiguous {dt} [{n}] tensor (ops.contrib_state makes the dict)")
+
+
+def raster_contrib_workspace_bytes(n: int, views: int, width: int, height: int, max_instances: int) -> int:
+    return int(_lib.load().sixdgs_raster_contrib_workspace_bytes(int(n), int(views), int(width), int(height), int(max_instances)))
+
+
+@_on_device
+def raster_contrib(state, n: int, views: int, width: int, height: int, out: Optional[dict] = None, *, want_views: bool = False,
+                   workspace: Optional[torch.Tensor] = None, profile: Optional[Profile] = None) -> dict:
+    """Every Gaussian's contribution to the views of one forward (sixdgs_raster_contrib in include/sixdgs.h defines it): state = the
+    (workspace, capacity) pair of raster_views(..., want_state=True) on n Gaussians and `views` rows at width x height, not written
+    since.  out: the accumulators, UPDATED IN PLACE -- ops.contrib_state's dict or a part of it (a missing key is not computed); None
+    starts from zeros.  Returns out, with want_views plus view_weight float32 [V,N] and view_pixels int32 [V,N] (written)."""
+    if (not isinstance(state, (tuple, list)) or len(state) != 2 or not torch.is_tensor(state[0])
+            or not 1 <= int(state[1]) <= RASTER_MAX_INSTANCES):
+        raise ValueError("state must be the (workspace, capacity) pair of raster_views(..., want_state=True)")
+    fwd_ws, capacity = state[0], int(state[1])
+    n, views, width, height = int(n), int(views), int(width), int(height)
+    if n < 0 or views < 0 or width < 1 or height < 1:
+        raise ValueError(f"n and views must not be negative, width and height positive (got {n}, {views}, {width} x {height})")
+    dev = fwd_ws.device
+    if out is None:
+        out = contrib_state(n, dev)
+    _check_contrib(out, n)
+    _need_gpu(fwd_ws, workspace, *out.values())
+    lib = _lib.load()
+    need = lib.sixdgs_raster_contrib_workspace_bytes(n, views, width, height, capacity)
+    if need == 0:
+        raise ValueError(f"sizes outside the rasteriser's limits (n {n}, views {views}, {width} x {height}, instances {capacity})")
+    ws, ws_bytes = _workspace(workspace, need, dev)
+    res = dict(out)
+    if want_views:
+        res.update({k: torch.zeros(views, n, dtype=dt, device=dev) for k, dt in CONTRIB_VIEWS})
+    check(lib.sixdgs_raster_contrib(n, views, width, height, capacity, _p(fwd_ws), fwd_ws.numel() * fwd_ws.element_size(),
+                                    *[_p(res.get(k)) for k, _ in CONTRIB + CONTRIB_VIEWS], _p(ws), ws_bytes, _stream(), profile),
+          "raster_contrib")
+    return res
+
+
+def scene_contrib_workspace_bytes(n: int, chunk: int, width: int, height: int, max_instances: int) -> int:
+    return int(_lib.load().sixdgs_scene_contrib_workspace_bytes(int(n), int(chunk), int(width), int(height), int(max_instances)))
+
+
+@_on_device
+def scene_contrib_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: torch.Tensor, width: int, height: int, *,
+                      chunk: int = 8, want_views: bool = False, scale_modifier: float = 1.0, scale_is_log: bool = True,
+                      opacity_is_logit: bool = True, max_instances: Optional[int] = None, retry: bool = True,
+                      workspace: Optional[torch.Tensor] = None) -> dict:
+    """Every Gaussian's contribution to the views cams [V,16] as ONE library call (sixdgs_scene_contrib in include/sixdgs.h): chunks of
+    `chunk` views, each projected, sorted and walked on the device, nothing read back in between.  max_instances is the capacity of
+    one chunk.  Returns a dict: the accumulators of CONTRIB from zero (weight, peak float32 [N]; pixels, stops int64 [N]; seen int32
+    [N]), with want_views view_weight float32 [V,N] and view_pixels int32 [V,N], status (int32 [1]; bit 1: a chunk did not fit the
+    capacity and is missing from the sums), instances_needed and max_instances (ints).  The call reads status and instances_needed
+    once at the end and -- with retry -- on bit 1 starts again from zeros with the needed capacity."""
+    if isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError(f"chunk must be a positive integer (got {chunk!r})")
+    cams, width, height = _view_args(cams, width, height, (0.0, 0.0, 0.0), scale_modifier)
+    scene, n, n_coef = _scene(xyz, scale, rot, opacity, f_dc, f_rest)
+    views = cams.shape[0]
+    chunk = max(min(int(chunk), views), 1)
+    capacity = _capacity(max_instances, n, chunk)
+    _need_gpu(*scene, cams, workspace)
+    lib = _lib.load()
+    dev = scene[0].device
+    out = contrib_state(n, dev)
+    if want_views:
+        out.update({k: torch.zeros(views, n, dtype=dt, device=dev) for k, dt in CONTRIB_VIEWS})
+    out["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    needed_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    needed = 0
+    for attempt in range(2):
+        need = lib.sixdgs_scene_contrib_workspace_bytes(n, chunk, width, height, capacity)
+        if need == 0:
+            raise ValueError(f"sizes outside the rasteriser's limits (n {n}, chunk {chunk}, {width} x {height}, instances {capacity})")
+        ws, ws_bytes = _workspace(workspace, need, dev)
+        check(lib.sixdgs_scene_contrib(*_scene_args(scene, n_coef, scale_is_log, opacity_is_logit), int(sh_degree), int(n_coef), n, _p(cams),
+                                       views, width, height, float(scale_modifier), chunk, capacity,
+                                       *[_p(out.get(k)) for k, _ in CONTRIB + CONTRIB_VIEWS], _p(out["status"]), _p(needed_t), _p(ws), ws_bytes,
+                                       _stream()),
+              "scene_contrib")
+        if views == 0:
+            break
+        # the one host read of the call: the status word and the largest instance count seen
+        flags = torch.cat([out["status"].to(torch.int64), needed_t]).cpu()
+        needed = int(flags[1])
+        if not retry or not int(flags[0]) & CONTRIB_STATUS_CAPACITY:
+            break
+        if attempt == 1 or needed > RASTER_MAX_INSTANCES:
+            raise RuntimeError(f"6dgs_amd: scene_contrib needs {needed} tile instances per chunk (limit 2^31 - 1): use a smaller chunk")
+        capacity = needed
+        for k, _ in CONTRIB:           # the chunks that fitted are in the sums already
+            out[k].zero_()
+    out["instances_needed"] = needed
+    out["max_instances"] = capacity
+    return out
+
+
 def photometric_loss_workspace_bytes(views: int, width: int, height: int, want_grad: bool = False) -> int:
     return int(_lib.load().sixdgs_photometric_loss_workspace_bytes(int(views), int(width), int(height), int(bool(want_grad))))
 

@@ -16,6 +16,9 @@ host sync is the ragged ray count, where the reference syncs too.  Extensions be
                    SURVEY 8(e) fallback).  The normals still come from the 20-NN search over ALL selected ellipsoids, so the
                    concatenation of the shards' rays in rank order IS the unsharded ray set.  Blocks are whole multiples of 256
                    ellipsoids (every shard's first ray then sits on a key-tile boundary of the unsharded scene).
+  importance       a non-negative [N] tensor (contribution.scene_contribution's weight, say): only valid ellipsoids of positive
+                   importance are candidates, and without perm the subsample is torch.multinomial over their importance, without
+                   replacement, in place of randperm; None is the reference's uniform draw
 """
 from __future__ import annotations
 
@@ -33,6 +36,30 @@ def shard_block(n: int, rank: int, world: int, granule: int = 256):
     return min(rank * per, n), min((rank + 1) * per, n)
 
 
+def _select_by_importance(valid_ids, importance, n: int, max_ellipsoids, perm):
+    """The emitting Gaussians when an importance is given: the candidates are the valid ellipsoids of positive importance, in index
+    order; all of them (max_ellipsoids None or negative), those a given perm picks from that list, or a draw without replacement
+    with probability proportional to the importance."""
+    dev = valid_ids.device
+    if not torch.is_tensor(importance) or tuple(importance.shape) != (n,) or importance.dtype == torch.bool:
+        raise ValueError(f"importance must be a [{n}] tensor of non-negative numbers")
+    w = importance.detach().to(device=dev, dtype=torch.float32)
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("importance must be finite and non-negative")
+    cand = valid_ids[w[valid_ids] > 0]
+    count = int(cand.shape[0])
+    take_all = max_ellipsoids is None or max_ellipsoids < 0
+    if perm is not None:
+        p = perm.to(dev)
+        return cand[p] if take_all else cand[p[: min(max_ellipsoids, count)]]
+    if take_all:
+        return cand
+    k = min(max_ellipsoids, count)
+    if k == 0:
+        return cand[:0]
+    return cand[torch.multinomial(w[cand], k, replacement=False)]
+
+
 @torch.no_grad()
 def generate_all_possible_rays(
     model,
@@ -46,6 +73,7 @@ def generate_all_possible_rays(
     k_neighbors: int = 20,
     return_src: bool = False,
     shard: Optional[tuple] = None,
+    importance: Optional[torch.Tensor] = None,
 ):
     xyz, log_scale, rot = model._xyz, model._scaling, model._rotation
     if not xyz.is_cuda:
@@ -54,7 +82,9 @@ def generate_all_possible_rays(
     mask_valid = ops.mask_degraded(log_scale, 50)
     valid_ids = torch.nonzero(mask_valid)[:, 0]
     valid_num = int(valid_ids.shape[0])
-    if max_ellipsoids is None or max_ellipsoids < 0:
+    if importance is not None:
+        sel = _select_by_importance(valid_ids, importance, xyz.shape[0], max_ellipsoids, perm)
+    elif max_ellipsoids is None or max_ellipsoids < 0:
         if perm is None:
             sel = valid_ids
         else:

@@ -209,6 +209,27 @@ class GaussianScene:
             setattr(self, k, getattr(self, k).to(device))
         return self
 
+    def subset(self, keep):
+        """A new scene of the Gaussians `keep` selects, in the same order: a bool mask [N], or ascending int64 indices without
+        repeats.  It carries max_sh_degree and active_sh_degree; this scene is not written and shares no memory with the result."""
+        n = len(self)
+        keep = torch.as_tensor(keep, device=self._xyz.device)
+        if keep.dtype == torch.bool:
+            if tuple(keep.shape) != (n,):
+                raise ValueError(f"a mask must be [{n}] (got {tuple(keep.shape)})")
+            idx = torch.nonzero(keep)[:, 0]
+        elif keep.dtype in (torch.int32, torch.int64) and keep.dim() == 1:
+            idx = keep.to(torch.int64)
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n or (idx.numel() > 1 and bool((idx[1:] <= idx[:-1]).any()))):
+                raise ValueError(f"indices must ascend strictly within [0, {n})")
+        else:
+            raise ValueError(f"keep must be a bool mask or a 1-D integer index tensor (got {keep.dtype}, {tuple(keep.shape)})")
+        s = type(self)(self.max_sh_degree)
+        s.active_sh_degree = self.active_sh_degree
+        for k in ("_xyz", "_scaling", "_rotation", "_features_dc", "_features_rest", "_opacity"):
+            setattr(s, k, getattr(self, k).detach()[idx].contiguous())
+        return s
+
     @property
     def device(self):
         return self._xyz.device

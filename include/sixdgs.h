@@ -282,6 +282,66 @@ int sixdgs_raster_views_backward(const float* xyz, const float* scale, int scale
                                  void* ws, size_t ws_bytes, sixdgs_stream_t stream, sixdgs_profile* prof);
 
 /* ---------------------------------------------------------------------------------------------
+ * Every Gaussian's contribution to views (additive in ABI 10): what step 11 of sixdgs_raster_views computes per (pixel, Gaussian) and
+ * drops -- alpha T -- kept per (view, Gaussian), with the number of pixels that added the Gaussian and the number it stopped.  A direct
+ * measurement: no gradient, no colour, no clamp in the way.  All arithmetic in fp32.
+ *
+ * fwd_ws is the workspace of a COMPLETED sixdgs_raster_views call with the same n, views, width, height and max_instances, whose
+ * instance count fitted, not written since (whether that call produced an image does not matter; the scene and cams are in fwd_ws
+ * already and are not passed again).  For view v and pixel (x, y) inside the image the walk of step 11 is repeated operation by
+ * operation over the same ordered list, so that every skip and the stop fall exactly where the forward's did:
+ *   1. d, power, the skip when power > 0, alpha = min(0.99, o exp(power)), the skip when alpha < 1/255, T' = T (1 - alpha);
+ *   2. when T' < 1e-4 the pixel stops: Gaussian j is counted as a STOP of this pixel and adds nothing;
+ *   3. otherwise the pixel ADDS j: w = alpha T, one fp32 product, T the value before j; then T = T'.
+ * Per (view v, Gaussian i), over the pixels of the tiles of i's rectangle (step 7):
+ *   weight_vi = the sum of w.  Within a tile in the backward's fixed tree: the 256 pixels in 4 groups of 64 in rows-of-16 order, within
+ *               a group x += x_(l xor s), s = 32 .. 1, then the groups in order; a pixel that does not add i (skipped, stopped, or
+ *               outside the image) counts as 0.f.  Then the tiles in rectangle order, from 0.f;
+ *   peak_vi   = the largest w (exact: it does not depend on any order), 0.f when there is none;
+ *   pixels_vi = the number of pixels that added i (int32);   stops_vi = the number of pixels i stopped (int32).
+ * Outputs, each may be NULL, [n] arrays, READ, UPDATED AND WRITTEN BACK over the views in ascending order, like sixdgs_densify_stats --
+ * the caller zeroes them, and a result does not depend on how the views are cut into calls:
+ *   weight (fp32)  ((weight + weight_v0) + weight_v1) ...        peak (fp32)   max(peak, peak_v)
+ *   pixels (int64) += pixels_v       stops (int64) += stops_v    seen (int32)  += (pixels_v > 0)
+ * and per view, WRITTEN, NOT ACCUMULATED: view_weight [views][n] fp32 = weight_vi, view_pixels [views][n] int32 = pixels_vi; a culled
+ * (view, Gaussian) gets exact zeros in both and changes no accumulator.
+ * SAME INPUT, SAME BYTES on every call: one owner per instance slot and per output, no floating-point atomics, no atomics at all.  VIEWS
+ * DO NOT MIX: view_weight[v], view_pixels[v] and view v's terms are the same bits whether v is walked alone or in a batch.  fwd_ws IS
+ * NOT WRITTEN.  If the recorded instance total exceeds max_instances the kernels read that on the device and return with EVERY OUTPUT
+ * UNTOUCHED (the per-view rows included).
+ * Limits and argument errors are the forward's, plus a NULL fwd_ws (SIXDGS_E_BADARG), misaligned outputs (4 bytes, the int64 arrays 8)
+ * and a workspace smaller than sixdgs_raster_views_workspace_bytes / sixdgs_raster_contrib_workspace_bytes say (SIXDGS_E_WORKSPACE):
+ * all answered without touching a GPU.  views == 0 or n == 0 returns 0; so does a call with every output NULL.
+ * sixdgs_raster_contrib_workspace_bytes is answered without a GPU and is 0 outside the limits: 16 B per instance (max_instances slots of
+ * sum, max, adds and stops), rounded up to 256.  One 256-thread workgroup per tile and view, one pixel per lane, the list staged through
+ * LDS in rounds of 256; after a round, thread k writes the round's k-th instance's own slot -- every slot exactly once, zeros in rounds
+ * behind the point where every pixel of the tile has stopped; then one lane per Gaussian sums its slots.  prof (may be NULL) receives
+ * one slot per stage: walk, gather.
+ *
+ * sixdgs_scene_contrib measures many views as one call.  Scene arrays, flags, sh_degree and scale_modifier as sixdgs_raster_views takes
+ * them; cams [views][16].  No image is formed, so there is no background.  It zeroes status[0] and instances_needed[0] -- NOT the
+ * accumulators, which are the caller's as above --, then for each chunk of up to `chunk` (>= 1) consecutive rows of cams enqueues on
+ * `stream`, through the entry points as they are: sixdgs_raster_views of the chunk's rows with no image and no radii (project, scan,
+ * emit, sort and ranges; the blend does not run; the count stays on the device), sixdgs_raster_contrib into the accumulators and -- when
+ * given -- the chunk's rows of view_weight / view_pixels, and a record: instances_needed[0] = max(instances_needed[0], count); if
+ * count > max_instances, bit 1 of status[0] is set and that chunk leaves the accumulators and its per-view rows as they were; other
+ * chunks are unaffected.  No host synchronisation, no device-to-host copy, no allocation; when it returns, the work is enqueued.  Given a
+ * capacity that fits, every output is the same bits for every chunk.  Limits and errors are the parts'; views == 0 returns 0, n == 0
+ * after the zeroing.  sixdgs_scene_contrib_workspace_bytes is answered without a GPU and is 0 outside the limits: the two parts'
+ * workspaces at `chunk` views and the count, each piece rounded up to 256 B. */
+size_t sixdgs_raster_contrib_workspace_bytes(int64_t n, int views, int width, int height, int64_t max_instances);
+int sixdgs_raster_contrib(int64_t n, int views, int width, int height, int64_t max_instances, const void* fwd_ws, size_t fwd_ws_bytes,
+                          float* weight /*[n]*/, float* peak /*[n]*/, int64_t* pixels /*[n]*/, int64_t* stops /*[n]*/,
+                          int32_t* seen /*[n]*/, float* view_weight /*[views][n] or NULL*/, int32_t* view_pixels /*[views][n] or NULL*/,
+                          void* ws, size_t ws_bytes, sixdgs_stream_t stream, sixdgs_profile* prof);
+size_t sixdgs_scene_contrib_workspace_bytes(int64_t n, int chunk, int width, int height, int64_t max_instances);
+int sixdgs_scene_contrib(const float* xyz, const float* scale, int scale_is_log, const float* rot, const float* opacity, int opacity_is_logit,
+                         const float* f_dc, const float* f_rest, int sh_degree, int n_coef, int64_t n, const float* cams /*[views][16]*/,
+                         int views, int width, int height, float scale_modifier, int chunk, int64_t max_instances, float* weight,
+                         float* peak, int64_t* pixels, int64_t* stops, int32_t* seen, float* view_weight, int32_t* view_pixels,
+                         int32_t* status /*[1]*/, int64_t* instances_needed /*[1]*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The photometric loss of render-and-compare (additive in ABI 10): per view loss_v = (1 - lambda) L1 + lambda (1 - SSIM) between an
  * image a and a target b, and grad_image = grad_loss[v] d loss_v / d a.  It is the reference's training objective (train.py:119 with
  * lambda_dssim = 0.2; utils/loss_utils.py: 11 x 11 Gaussian window, sigma 1.5, padding 5, one group per channel).  All arithmetic in
