@@ -120,8 +120,9 @@ def _blend_tile(conic, u, v, colour, o, g, xs, ys, bg):
     return torch.stack([C[0] + T * bg[0], C[1] + T * bg[1], C[2] + T * bg[2], 1 - T], dim=1)
 
 
-def render(t, rows, width, height, sh_degree, background=RR.BACKGROUND, scale_modifier=1.0):
-    """image_f32 [V,H,W,4] of the tensors t (xyz, log_scale, rot, opacity, f_dc, f_rest) and rows [V,16], all of one dtype."""
+def render(t, rows, width, height, sh_degree, background=RR.BACKGROUND, scale_modifier=1.0, scale_is_log=True, opacity_is_logit=True):
+    """image_f32 [V,H,W,4] of the tensors t (xyz, log_scale, rot, opacity, f_dc, f_rest) and rows [V,16], all of one dtype.
+    scale_is_log / opacity_is_logit off: t["log_scale"] / t["opacity"] hold the raw values (RR.project)."""
     dt = rows.dtype
     npdt = np.float64 if dt == torch.float64 else np.float32
     scene = {k: t[k].detach().numpy().astype(np.float32) for k in NAMES[:-1]}
@@ -130,12 +131,13 @@ def render(t, rows, width, height, sh_degree, background=RR.BACKGROUND, scale_mo
     images = []
     for vw in range(rows.shape[0]):
         row = rows[vw].detach().numpy().astype(np.float32)
-        P = RR.project(scene, row, width, height, npdt, scale_modifier)
+        P = RR.project(scene, row, width, height, npdt, scale_modifier, scale_is_log, opacity_is_logit)
         gx, gy = P["gx"], P["gy"]
         live = np.nonzero(P["live"])[0]
         where = np.full(P["n"], -1, np.int64)
         where[live] = np.arange(live.shape[0])
-        conic, u, v, colour, o = _project(t, rows[vw], torch.from_numpy(live), width, height, sh_degree, scale_modifier)
+        conic, u, v, colour, o = _project(t, rows[vw], torch.from_numpy(live), width, height, sh_degree, scale_modifier,
+                                          scale_is_log, opacity_is_logit)
         tile, gid = RR._instances(P["rect"], live, gx)
         order = np.lexsort((gid, P["z"][gid], tile))
         tile, gid = tile[order], where[gid[order]]
@@ -151,12 +153,12 @@ def render(t, rows, width, height, sh_degree, background=RR.BACKGROUND, scale_mo
     return torch.stack(images)
 
 
-def gradients(scene, rows, width, height, dtype, g, background=RR.BACKGROUND, scale_modifier=1.0):
+def gradients(scene, rows, width, height, dtype, g, background=RR.BACKGROUND, scale_modifier=1.0, scale_is_log=True, opacity_is_logit=True):
     """-> dict: image [V,H,W,4] and the gradient of sum(g * image) by each of NAMES, as numpy arrays of `dtype`."""
     dt = torch.float64 if np.dtype(dtype) == np.float64 else torch.float32
     t = {k: torch.from_numpy(np.ascontiguousarray(scene[k], np.float32)).to(dt).requires_grad_(True) for k in NAMES[:-1]}
     cams = torch.from_numpy(np.ascontiguousarray(rows, np.float32)).to(dt).requires_grad_(True)
-    image = render(t, cams, width, height, int(scene["sh_degree"]), background, scale_modifier)
+    image = render(t, cams, width, height, int(scene["sh_degree"]), background, scale_modifier, scale_is_log, opacity_is_logit)
     (image * torch.from_numpy(np.ascontiguousarray(g, np.float32)).to(dt)).sum().backward()
     out = {k: (t[k].grad if t[k].grad is not None else torch.zeros_like(t[k])).numpy() for k in NAMES[:-1]}
     out["cams"] = (cams.grad if cams.grad is not None else torch.zeros_like(cams)).numpy()
@@ -184,15 +186,42 @@ def bounds(g64, g32):
 _cache = {}
 
 
-def case(syn, n, scene_seed, views, cam_seed, width, height, sh_degree=3):
-    """RR.case of the same key, the loss weights and both restatements' gradients, computed once per session (read-only)."""
-    key = (n, scene_seed, views, cam_seed, width, height, sh_degree)
+def measure(rr, width, height, **kw):
+    """Of an RR.measure / RR.case result rr (kw: the switches it was made with): the loss weights and both restatements' gradients,
+    frozen -> the dict case() returns."""
+    views = rr["rows"].shape[0]
+    g = loss_weights((views, height, width, 4), rr["undecidable"])
+    g64 = gradients(rr["scene"], rr["rows"], width, height, np.float64, g, **kw)
+    g32 = gradients(rr["scene"], rr["rows"], width, height, np.float32, g, **kw)
+    for a in (g, *g64.values(), *g32.values()):
+        a.setflags(write=False)
+    return {"scene": rr["scene"], "rows": rr["rows"], "rr": rr, "g": g, "g64": g64, "g32": g32, "bounds": bounds(g64, g32)}
+
+
+def case(syn, n, scene_seed, views, cam_seed, width, height, sh_degree=3, *, stored_degree=None, scale_is_log=True, opacity_is_logit=True,
+         scale_modifier=1.0):
+    """RR.case of the same arguments, the loss weights and both restatements' gradients, computed once per session (read-only)."""
+    kw = dict(scale_is_log=bool(scale_is_log), opacity_is_logit=bool(opacity_is_logit), scale_modifier=float(scale_modifier))
+    key = (n, scene_seed, views, cam_seed, width, height, sh_degree, sh_degree if stored_degree is None else stored_degree, *kw.values())
     if key not in _cache:
-        c = RR.case(syn, *key)
-        g = loss_weights((views, height, width, 4), c["undecidable"])
-        g64 = gradients(c["scene"], c["rows"], width, height, np.float64, g)
-        g32 = gradients(c["scene"], c["rows"], width, height, np.float32, g)
-        for a in (g, *g64.values(), *g32.values()):
-            a.setflags(write=False)
-        _cache[key] = {"scene": c["scene"], "rows": c["rows"], "rr": c, "g": g, "g64": g64, "g32": g32, "bounds": bounds(g64, g32)}
+        _cache[key] = measure(RR.case(syn, *key[:7], stored_degree=stored_degree, **kw), width, height, **kw)
     return _cache[key]
+
+
+# the parameterisations sixdgs_raster_views accepts beyond the stored-log, stored-logit, modifier-1, full-degree corner of CASES: all on
+# 300 Gaussians, 2 views, 40 x 24 (partial tiles on both axes).  (name, positional arguments of case(), keyword arguments of case())
+PARAM_BASE = (300, 2, 2, 3, 40, 24)
+PARAM_CASES = (
+    ("degree 0 of 16", PARAM_BASE + (0,), dict(stored_degree=3)),
+    ("degree 1 of 4", PARAM_BASE + (1,), {}),
+    ("degree 1 of 16", PARAM_BASE + (1,), dict(stored_degree=3)),
+    ("degree 2 of 9", PARAM_BASE + (2,), {}),
+    ("degree 2 of 16", PARAM_BASE + (2,), dict(stored_degree=3)),
+    ("raw scale", PARAM_BASE + (3,), dict(scale_is_log=False)),
+    ("raw opacity", PARAM_BASE + (3,), dict(opacity_is_logit=False)),
+    ("raw scale, raw opacity, degree 1 of 16", PARAM_BASE + (1,), dict(stored_degree=3, scale_is_log=False, opacity_is_logit=False)),
+    ("modifier 0.5", PARAM_BASE + (3,), dict(scale_modifier=0.5)),
+    ("modifier 1.7", PARAM_BASE + (3,), dict(scale_modifier=1.7)),
+    ("raw scale, modifier 0.5", PARAM_BASE + (3,), dict(scale_is_log=False, scale_modifier=0.5)),
+    ("raw scale, modifier 1.7", PARAM_BASE + (3,), dict(scale_is_log=False, scale_modifier=1.7)),
+)

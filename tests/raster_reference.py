@@ -83,8 +83,10 @@ def _tile_bound(q, g):
     return np.clip(np.trunc(np.clip(q, -1.0, g + 1.0)).astype(np.int64), 0, g)
 
 
-def project(scene, row, width, height, dt, scale_modifier=1.0):
-    """Steps 1-9 for one view, over the Gaussians with p.z above the band below 0.2.  Returns a dict of arrays over ALL n Gaussians."""
+def project(scene, row, width, height, dt, scale_modifier=1.0, scale_is_log=True, opacity_is_logit=True):
+    """Steps 1-9 for one view, over the Gaussians with p.z above the band below 0.2.  Returns a dict of arrays over ALL n Gaussians.
+    scale_is_log / opacity_is_logit off: scene["log_scale"] / scene["opacity"] hold the raw scales / opacities, used as they are.
+    scene["sh_degree"] may be below the degree scene["f_rest"] stores: the coefficients past it are not evaluated."""
     dt = np.dtype(dt).type
     f = lambda a: np.asarray(a, np.float32).astype(dt)      # noqa: E731
     n = scene["xyz"].shape[0]
@@ -100,7 +102,8 @@ def project(scene, row, width, height, dt, scale_modifier=1.0):
     px = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3]
     py = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7]
     # 2. Sigma = M M^T, M = R S
-    s = dt(scale_modifier) * np.exp(f(scene["log_scale"])[ids])
+    s = f(scene["log_scale"])[ids]
+    s = dt(scale_modifier) * (np.exp(s) if scale_is_log else s)
     M = _rotmat(f(scene["rot"])[ids]) * s[:, None, :]
     S = np.empty((ids.shape[0], 3, 3), dt)
     for r in range(3):
@@ -154,7 +157,7 @@ def project(scene, row, width, height, dt, scale_modifier=1.0):
     sh[:, 1:1 + rest.shape[1]] = rest
     colour = _sh_colour(sh, int(scene["sh_degree"]), dx / nrm, dy / nrm, dz / nrm).astype(dt)
     op = f(scene["opacity"]).reshape(-1)[ids]
-    o = dt(1) / (dt(1) + np.exp(-op))
+    o = dt(1) / (dt(1) + np.exp(-op)) if opacity_is_logit else op
 
     def full(vals, fill=0):
         arr = np.full((n,) + vals.shape[1:], fill, vals.dtype)
@@ -253,12 +256,13 @@ def _blend_tile(P, g, maybe, swapped, xs, ys, background, dt):
     return np.concatenate([np.stack(C, axis=1) + T[:, None] * bg[None, :], (dt(1) - T)[:, None]], axis=1), und
 
 
-def reference_view(scene, row, width, height, dtype=np.float64, scale_modifier=1.0, background=(1.0, 1.0, 1.0), tiles=None):
+def reference_view(scene, row, width, height, dtype=np.float64, scale_modifier=1.0, background=(1.0, 1.0, 1.0), tiles=None,
+                   scale_is_log=True, opacity_is_logit=True):
     """One view -> dict: image [H,W,4] (dtype), undecidable [H,W], radii [n], rect [n,4], decidable [n], instances (int), and
     instances_lo / instances_hi (what the count may be once the undecidable rectangles are taken either way).
     tiles: only these tile numbers are blended (the others keep the background and are marked in `blended` [H,W] as False)."""
     dt = np.dtype(dtype).type
-    P = project(scene, row, width, height, dt, scale_modifier)
+    P = project(scene, row, width, height, dt, scale_modifier, scale_is_log, opacity_is_logit)
     other = np.float32 if dt is np.float64 else np.float64
     z_other = _depth(scene["xyz"], row, other).astype(np.float64)
     z_own = P["z"].astype(np.float64)
@@ -328,22 +332,45 @@ def reference_views(scene, rows, width, height, dtype=np.float64, **kw):
 _cache = {}
 
 
-def case(syn, n, scene_seed, views, cam_seed, width, height, sh_degree=3):
-    """The scene, the camera rows and both restatements of one case, computed once per session and shared (read-only)."""
-    key = (n, scene_seed, views, cam_seed, width, height, sh_degree)
+def raw_scene(scene, scale_is_log=True, opacity_is_logit=True):
+    """The scene with its scales / opacities stored raw where the switch is off: exp / sigmoid of the stored fp32 numbers taken in fp64
+    and rounded to the fp32 the kernel gets (still under the keys "log_scale" / "opacity")."""
+    out = dict(scene)
+    if not scale_is_log:
+        out["log_scale"] = np.exp(scene["log_scale"].astype(np.float64)).astype(np.float32)
+    if not opacity_is_logit:
+        out["opacity"] = (1.0 / (1.0 + np.exp(-scene["opacity"].astype(np.float64)))).astype(np.float32)
+    return out
+
+
+def measure(scene, rows, width, height, **kw):
+    """Both restatements of a scene (kw: scale_modifier, scale_is_log, opacity_is_logit), frozen -> the dict case() returns."""
+    r64 = reference_views(scene, rows, width, height, np.float64, background=BACKGROUND, **kw)
+    r32 = reference_views(scene, rows, width, height, np.float32, background=BACKGROUND, **kw)
+    und = r64["undecidable"] | r32["undecidable"]
+    dec = r64["decidable"] & r32["decidable"]
+    diff = np.abs(r32["image"].astype(np.float64) - r64["image"])[~und]
+    for a in (und, dec, *r64.values(), *r32.values()):
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return {"scene": scene, "rows": rows, "r64": r64, "r32": r32, "undecidable": und, "decidable": dec,
+            "rounding": float(diff.max()) if diff.size else 0.0}
+
+
+def case(syn, n, scene_seed, views, cam_seed, width, height, sh_degree=3, *, stored_degree=None, scale_is_log=True, opacity_is_logit=True,
+         scale_modifier=1.0):
+    """The scene, the camera rows and both restatements of one case, computed once per session and shared (read-only).
+    stored_degree D >= sh_degree: the scene is make_scene's of degree D, rendered at sh_degree.  scale_is_log / opacity_is_logit off:
+    the scene is raw_scene's."""
+    stored = sh_degree if stored_degree is None else stored_degree
+    assert stored >= sh_degree
+    key = (n, scene_seed, views, cam_seed, width, height, sh_degree, stored, bool(scale_is_log), bool(opacity_is_logit), float(scale_modifier))
     if key not in _cache:
-        scene = syn.make_scene(n, scene_seed, sh_degree=sh_degree)
+        scene = raw_scene(syn.make_scene(n, scene_seed, sh_degree=stored), scale_is_log, opacity_is_logit)
+        scene["sh_degree"] = np.int64(sh_degree)
         rows = camera_rows(syn.make_cameras(views, cam_seed, width=width, height=height))
-        r64 = reference_views(scene, rows, width, height, np.float64, background=BACKGROUND)
-        r32 = reference_views(scene, rows, width, height, np.float32, background=BACKGROUND)
-        und = r64["undecidable"] | r32["undecidable"]
-        dec = r64["decidable"] & r32["decidable"]
-        diff = np.abs(r32["image"].astype(np.float64) - r64["image"])[~und]
-        for a in (und, dec, *r64.values(), *r32.values()):
-            if isinstance(a, np.ndarray):
-                a.setflags(write=False)
-        _cache[key] = {"scene": scene, "rows": rows, "r64": r64, "r32": r32, "undecidable": und, "decidable": dec,
-                       "rounding": float(diff.max()) if diff.size else 0.0}
+        _cache[key] = measure(scene, rows, width, height, scale_modifier=scale_modifier, scale_is_log=scale_is_log,
+                              opacity_is_logit=opacity_is_logit)
     return _cache[key]
 
 

@@ -63,11 +63,11 @@ def same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
-def by_hand(ops, f, target, quantise):
-    """ops.raster_views followed by ops.image_metrics, one view at a time."""
+def by_hand(ops, f, target, quantise, sh_degree=3, width=WIDTH, height=HEIGHT, **raster):
+    """ops.raster_views followed by ops.image_metrics, one view at a time; raster: scale_modifier, scale_is_log and opacity_is_logit."""
     rows, renders = [], []
-    for v in range(VIEWS):
-        image = ops.raster_views(*f["arrays"], 3, f["rows"][v:v + 1].contiguous(), WIDTH, HEIGHT, want_float=True, want_u8=False)
+    for v in range(f["rows"].shape[0]):
+        image = ops.raster_views(*f["arrays"], sh_degree, f["rows"][v:v + 1].contiguous(), width, height, want_float=True, want_u8=False, **raster)
         m, r = ops.image_metrics(image, target[v:v + 1].contiguous(), quantise=quantise, want_render=True)
         rows.append(m)
         renders.append(r)

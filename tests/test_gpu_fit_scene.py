@@ -66,8 +66,9 @@ def schedule(steps, batch):
     return views, lrs, degrees, resets
 
 
-def hand_loop(ops, p, rows, target, views, lrs, degrees, resets, groups, capacity, lam=0.2, eps=1e-15, ceiling=0.01):
-    """sixdgs_fit_scene composed in Python from its parts, on the dict p (in place)."""
+def hand_loop(ops, p, rows, target, views, lrs, degrees, resets, groups, capacity, lam=0.2, eps=1e-15, ceiling=0.01, **raster):
+    """sixdgs_fit_scene composed in Python from its parts, on the dict p (in place); raster: scale_modifier, scale_is_log and
+    opacity_is_logit of both rasteriser calls."""
     steps, batch = views.shape
     n, n_coef = p["xyz"].shape[0], 1 + p["f_rest"].shape[1]
     state = ops.gaussian_adam_state(p)
@@ -79,16 +80,17 @@ def hand_loop(ops, p, rows, target, views, lrs, degrees, resets, groups, capacit
         cams, tgt = rows[idx].contiguous(), target[idx].contiguous()
         scene = [p[k] for k in ORDER]
         image, needed, fwd = ops.raster_views(*scene, int(degrees[s]), cams, SIZE, SIZE, want_float=True, want_u8=False, want_instances=True,
-                                              want_state=True, max_instances=capacity)
+                                              want_state=True, max_instances=capacity, **raster)
         assert needed <= capacity and fwd[1] == capacity
         needed_max = max(needed_max, needed)
         loss, grad = ops.photometric_loss(image, tgt, lambda_dssim=lam, want_grad=True)
-        grads = ops.raster_views_backward(*scene, int(degrees[s]), cams, SIZE, SIZE, grad, fwd, want=tuple(k for k in ORDER if k in groups))
+        grads = ops.raster_views_backward(*scene, int(degrees[s]), cams, SIZE, SIZE, grad, fwd, want=tuple(k for k in ORDER if k in groups),
+                                          **raster)
         history[s] = loss
         ops.gaussian_adam(p, {k: g for k, g in zip(ops.RASTER_GRADIENTS, grads) if g is not None}, state, s, lrs[s], eps=eps,
                           instances=torch.tensor([needed], dtype=torch.int64, device="cuda"), max_instances=capacity)
         if resets[s]:
-            ops.opacity_reset(p["opacity"], state["m"][sl], state["v"][sl], ceiling=ceiling)
+            ops.opacity_reset(p["opacity"], state["m"][sl], state["v"][sl], ceiling=ceiling, opacity_is_logit=raster.get("opacity_is_logit", True))
     return dict(history=history, m=state["m"], v=state["v"], status=state["status"], instances_needed=needed_max)
 
 

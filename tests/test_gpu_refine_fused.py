@@ -131,21 +131,23 @@ def test_step_kernel_freezes_and_reports_capacity(ops):
     assert all(torch.equal(kept[k], state[k]) for k in kept if k not in ("status", "instances_needed"))
 
 
-def hand_loop(ops, tensors, sh_degree, start, width, height, target, steps, capacity, lam=0.2, **hyper):
-    """sixdgs_refine_poses composed in Python from its parts."""
+def hand_loop(ops, tensors, sh_degree, start, width, height, target, steps, capacity, lam=0.2, raster=None, **hyper):
+    """sixdgs_refine_poses composed in Python from its parts; raster: scale_modifier, scale_is_log and opacity_is_logit of both rasteriser
+    calls."""
+    raster = raster or {}
     views = start.shape[0]
     state = ops.pose_state(start)
     history = torch.empty(steps + 1, views, device="cuda")
     for step in range(steps + 1):
         last = step == steps
         image, needed, fwd = ops.raster_views(*tensors, sh_degree, state["rows"], width, height, want_float=True, want_u8=False, want_instances=True,
-                                              want_state=True, max_instances=capacity)
+                                              want_state=True, max_instances=capacity, **raster)
         assert needed <= capacity and fwd[1] == capacity
         if last:
             loss, d_rows = ops.photometric_loss(image, target, lambda_dssim=lam), None
         else:
             loss, grad = ops.photometric_loss(image, target, lambda_dssim=lam, want_grad=True)
-            d_rows = ops.raster_views_backward(*tensors, sh_degree, state["rows"], width, height, grad, fwd, want=("cams",))[6]
+            d_rows = ops.raster_views_backward(*tensors, sh_degree, state["rows"], width, height, grad, fwd, want=("cams",), **raster)[6]
         ops.pose_step(start, loss, d_rows, state, history[step], step, instances=torch.tensor([needed], dtype=torch.int64, device="cuda"),
                       max_instances=capacity, evaluate_only=last, **hyper)
     return dict(state, history=history, instances_needed=int(state["instances_needed"]))
