@@ -226,6 +226,8 @@ def emit_quadricell(xyz, scale, rot, f_dc, f_rest, sh_degree: int, sel: Optional
         f_dc, f_rest = _f32(f_dc), _f32(f_rest)
         n_coef = 1 + f_rest.shape[1]
         rgb = torch.empty(r, 3, device=dev)
+    else:
+        sh_degree = 0                       # no colour asked for: the degree names no coefficients (the entry point checks it against n_coef)
     if r:
         check(lib.sixdgs_emit_quadricell_write(_p(xyz), _p(scale), int(scale_is_log), _p(rot), _p(f_dc if want_rgb else None),
                                                _p(f_rest if want_rgb else None), int(sh_degree), int(n_coef), _p(sel_t), e,
@@ -272,6 +274,8 @@ def emit_isocell(xyz, scale, rot, f_dc, f_rest, sh_degree: int, sel, normals, di
     if want_rgb:
         f_dc, f_rest = _f32(f_dc), _f32(f_rest)
         n_coef = 1 + f_rest.shape[1]
+    else:
+        sh_degree = 0                       # as in emit_quadricell
     check(_lib.load().sixdgs_emit_isocell(_p(xyz), _p(scale), int(scale_is_log), _p(rot), _p(f_dc if want_rgb else None),
                                           _p(f_rest if want_rgb else None), int(sh_degree), int(n_coef), _p(sel_t), e,
                                           _p(normals), _p(dirs), k, _p(ori), _p(dr), _p(rgb), _p(src), _stream()), "emit_isocell")
