@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "lib6dgs_hip.so")
 HOSTCHECK = os.path.join(CSRC, "libsixdgs_hostcheck.so")
 SOURCES = ["geometry.hip", "gemm.hip", "dense.hip", "score.hip", "score_bwd.hip", "pose.hip", "pose_consensus.hip", "vit.hip", "splat.hip", "raster.hip", "photometric.hip", "refine.hip", "fit.hip", "densify.hip", "knn.hip", "pyramid.hip", "metrics.hip", "contrib.hip"]
-HEADERS = ["common.h", "device_math.h", "gemm_kernel.h", "dense.h", os.path.join("..", "..", "include", "sixdgs.h"), "dense_layout.h", "sweep_plan.h", "sweep_layout.h", "pose_step.h", "adam_step.h", "render_pass.h", "densify_rules.h", "knn_rules.h", "pyramid_rules.h"]
+HEADERS = ["common.h", "device_math.h", "gemm_kernel.h", "dense.h", os.path.join("..", "..", "include", "sixdgs.h"), "dense_layout.h", "sweep_plan.h", "sweep_layout.h", "pose_step.h", "adam_step.h", "render_pass.h", "densify_rules.h", "knn_rules.h", "pyramid_rules.h", "image_prep_rules.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 FLAGS += os.environ.get("SIXDGS_EXTRA_FLAGS", "").split()       # developer builds (e.g. -DSDG_DENSE_PROF: tools/prof_dense.py)
@@ -51,12 +51,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_hostcheck(force: bool = False) -> str:
-    """Host instantiation of device_math.h, dense_layout.h, pose_step.h, adam_step.h, densify_rules.h, knn_rules.h and pyramid_rules.h for the CPU test-suite (no GPU
+    """Host instantiation of device_math.h, dense_layout.h, pose_step.h, adam_step.h, densify_rules.h, knn_rules.h, pyramid_rules.h and image_prep_rules.h for the CPU test-suite (no GPU
     code inside)."""
     src = os.path.join(CSRC, "hostcheck.cpp")
     deps = [src, os.path.join(CSRC, "device_math.h"), os.path.join(CSRC, "dense_layout.h"), os.path.join(CSRC, "sweep_plan.h"),
             os.path.join(CSRC, "sweep_layout.h"), os.path.join(CSRC, "pose_step.h"), os.path.join(CSRC, "adam_step.h"), os.path.join(CSRC, "densify_rules.h"),
-            os.path.join(CSRC, "knn_rules.h"), os.path.join(CSRC, "pyramid_rules.h")]
+            os.path.join(CSRC, "knn_rules.h"), os.path.join(CSRC, "pyramid_rules.h"), os.path.join(CSRC, "image_prep_rules.h")]
     if force or _stale(HOSTCHECK, deps):
         cmd = [HIPCC, "-x", "hip", "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-shared", src,
                "-o", HOSTCHECK]

@@ -3,7 +3,7 @@
 // (the per-entry arithmetic of fitting a scene's Gaussians) behind a tiny C ABI, so the CPU test-suite can compare the product's arithmetic with the oracle and the
 // golden vectors without a GPU.  densify_rules.h (the per-entry rules of a densification round) and knn_rules.h (the pair and box rules
 // of the 3-nearest-neighbour search) are instantiated here too, and pyramid_rules.h (a level schedule's geometry, target value and
-// keep-the-input rule).  Contains no kernels; never used by the product path.
+// keep-the-input rule) and image_prep_rules.h (the spans, weights and launch plan of the one-pass image preparation).  Contains no kernels; never used by the product path.
 #include <stdlib.h>
 
 #include "device_math.h"
@@ -15,6 +15,7 @@
 #include "densify_rules.h"
 #include "knn_rules.h"
 #include "pyramid_rules.h"
+#include "image_prep_rules.h"
 
 #include <algorithm>
 #include <vector>
@@ -360,6 +361,35 @@ int hc_pyr_target(const unsigned char* images, int views, int H, int W, int C, i
 }
 void hc_pyr_keep_input(const float* best_loss_last, const float* loss_input, long long n, int* keep) {
   for (long long i = 0; i < n; ++i) keep[i] = pyr::keep_input(best_loss_last[i], loss_input[i]) ? 1 : 0;
+}
+// ---- image_prep_rules.h: spans, weights and the launcher's plan of sixdgs_image_prep (tests/test_image_prep_host.py) ----
+// plan5 = (kt, rb, nrmax, lds_bytes, supported); scales4 (may be NULL) = (sh, sw, sup_h, sup_w); returns supported
+int hc_ip_plan(int batch, int height, int width, int resized_h, int resized_w, int out_size, long long* plan5, float* scales4) {
+  const ip::Plan p = ip::plan(batch, height, width, resized_h, resized_w, out_size);
+  plan5[0] = p.kt; plan5[1] = p.rb; plan5[2] = p.nrmax; plan5[3] = (long long)p.lds_bytes; plan5[4] = p.supported ? 1 : 0;
+  if (scales4) { scales4[0] = p.sh; scales4[1] = p.sw; scales4[2] = p.sup_h; scales4[3] = p.sup_w; }
+  return p.supported ? 1 : 0;
+}
+// output indices i0 .. i0 + count of the resized grid along an axis of n samples: weights_out [count][kt], meta_out [count][2] = (xmin, min(xsize, kt))
+void hc_ip_spans(int i0, int count, int n, float scale, float support, int kt, float* weights_out, int* meta_out) {
+  for (int i = 0; i < count; ++i) ip::aa_weights(i0 + i, n, scale, support, kt, weights_out + (size_t)i * kt, meta_out + 2 * i);
+}
+// the same indices: xsize_out [count] = the span's size before aa_weights caps it at kt
+void hc_ip_span_sizes(int i0, int count, int n, float scale, float support, int* xsize_out) {
+  for (int i = 0; i < count; ++i) {
+    int xmin;
+    ip::aa_span(i0 + i, n, scale, support, xmin, xsize_out[i]);
+  }
+}
+// the largest row window r1 - r0 over the bands of rb output rows of a crop of out_size rows that starts at row `top` of the resized grid
+int hc_ip_max_window(int height, int top, int out_size, int rb, float sh, float sup_h, int kt) {
+  int worst = 0;
+  for (int oy0 = 0; oy0 < out_size; oy0 += rb) {
+    int r0, r1;
+    ip::band_window(top, oy0, std::min(rb, out_size - oy0), height, sh, sup_h, kt, r0, r1);
+    worst = std::max(worst, r1 - r0);
+  }
+  return worst;
 }
 int hc_dl_const(int which) {
   const int v[] = {dl::kSlabB, dl::kPRow, dl::kGran, dl::kGranSlab, dl::kChunkRun};

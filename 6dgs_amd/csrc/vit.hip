@@ -24,6 +24,7 @@
 // Orientation: C[feature][token] (weights = MFMA rows): a lane owns ONE token per accumulator and 4 consecutive features per register group, so the
 // token's scale is one factor per lane and the epilogue writes 16-byte pieces of a token's output row.
 #include "gemm_kernel.h"
+#include "image_prep_rules.h"
 #include <cstdlib>
 
 using namespace sdg;
@@ -593,7 +594,8 @@ __global__ void __launch_bounds__(256) k_u8_to_planar(const uint8_t* __restrict_
 // clipped to the input, weights filter((j + xmin - centre + 0.5) / scale) normalised by their sum in tap order; a window's rows are first reduced along x, then along y, each as
 // a tap-order sum that starts from the first product.  What differs is only WHO computes a row's x-reduction: here once per (input row, output column) of a band of
 // output rows, shared through LDS by the band's rows (separable), there once per output pixel.  The same products in the same order: equal up to the compiler's choice of
-// fused multiply-adds (tests: <= 2e-6 of the op's result on [-2.2, 2.7]-ranged values).
+// fused multiply-adds (tests: <= 5e-6 of the op's result on [-2.2, 2.7]-ranged values, and within 8 x the fp32 restatement's own distance from fp64 of
+// tests/image_prep_reference.py at every band height, border, output size and byte alignment).
 // One workgroup = (band of rb output rows, image).  LDS: table | wx [S][kt] | x spans | wy [rb][kt] | y spans | x-reduced rows [nr][3][S].
 struct PrepArgs {
   const uint8_t* in;
@@ -605,35 +607,8 @@ struct PrepArgs {
   int64_t last_dword;               // index of the last dword that holds image bytes (loads are clamped to it)
 };
 
-__device__ __forceinline__ float aa_cubic(float x) {      // upsample_antialias::BicubicFilterFunctor, a = -0.5
-  const float a = -0.5f;
-  x = fabsf(x);
-  if (x < 1.f) return ((a + 2.f) * x - (a + 3.f)) * x * x + 1.f;
-  if (x < 2.f) return (((x - 5.f) * x + 8.f) * x - 4.f) * a;
-  return 0.f;
-}
-
-// span and normalised weights of output index i (of the resized grid) along an axis of n input samples; w[0 .. kt): zero beyond xsize
-__device__ __forceinline__ void aa_weights(int i, int n, float scale, float support, int kt, float* w, int* meta) {
-  const float center = scale * ((float)i + 0.5f);
-  const int xmin = max((int)(center - support + 0.5f), 0);
-  const int xsize = min((int)(center + support + 0.5f), n) - xmin;
-  const float invscale = scale >= 1.f ? 1.f / scale : 1.f;
-  const float xmc = (float)xmin - center;
-  float total = 0.f;
-  for (int j = 0; j < kt; ++j) {
-    float v = 0.f;
-    if (j < xsize) {
-      v = aa_cubic(((float)j + xmc + 0.5f) * invscale);
-      total += v;
-    }
-    w[j] = v;
-  }
-  if (total != 0.f)
-    for (int j = 0; j < xsize && j < kt; ++j) w[j] /= total;
-  meta[0] = xmin;
-  meta[1] = xsize < kt ? xsize : kt;
-}
+// (the cubic, a span with its normalised weights, and the launcher's plan: image_prep_rules.h)
+using ip::aa_weights;
 
 __global__ void __launch_bounds__(256) k_image_prep(PrepArgs A) {
   extern __shared__ __attribute__((aligned(16))) float prep_sm[];
@@ -816,29 +791,18 @@ int sixdgs_image_prep(const uint8_t* images, int batch, int height, int width, c
   PrepArgs A;
   A.in = images; A.lut = table256; A.out = out;
   A.H = height; A.W = width; A.top = crop_top; A.left = crop_left; A.S = out_size;
-  A.sh = (float)height / (float)resized_h;                 // area_pixel_compute_scale, align_corners = false, no scale factor given
-  A.sw = (float)width / (float)resized_w;
-  A.sup_h = A.sh >= 1.f ? 2.f * A.sh : 2.f;                // (interp_size 4) / 2 * scale
-  A.sup_w = A.sw >= 1.f ? 2.f * A.sw : 2.f;
-  const float sup = A.sup_h > A.sup_w ? A.sup_h : A.sup_w;
-  const int taps = (int)ceilf(sup) * 2 + 1;                // the op's own window size
-  A.kt = (taps + 3) & ~3;
-  if (A.kt > 64) return SIXDGS_E_UNSUPPORTED;              // (scale > 15: not a query image of this pipeline)
+  const ip::Plan P = ip::plan(batch, height, width, resized_h, resized_w, out_size);      // scales, taps, band height, LDS rows and bytes
+  if (!P.supported) return SIXDGS_E_UNSUPPORTED;           // scale > 15, or not even a band of one output row fits the LDS budget
+  A.sh = P.sh; A.sw = P.sw; A.sup_h = P.sup_h; A.sup_w = P.sup_w;
+  A.kt = P.kt; A.rb = P.rb; A.nrmax = P.nrmax;
   for (int c = 0; c < 3; ++c) { A.mean[c] = mean3[c]; A.stdv[c] = std3[c]; }
   A.last_dword = ((int64_t)batch * height * width * 3 - 1) >> 2;
-  // band height: 8 output rows for batches that fill the chip anyway, 4 below (more workgroups, shorter each); fewer when the x-reduced rows do not fit 150 KB of LDS
-  size_t lds = 0;
-  for (A.rb = (int64_t)batch * sdg_cdiv(out_size, 8) >= 256 ? 8 : 4; A.rb >= 1; A.rb >>= 1) {
-    A.nrmax = (int)((float)A.rb * A.sh + 2.f * A.sup_h) + 3;
-    lds = sizeof(float) * (256 + (size_t)out_size * A.kt + 2 * (size_t)out_size + (size_t)A.rb * A.kt + 2 * (size_t)A.rb + (size_t)A.nrmax * 3 * out_size);
-    if (lds <= 150 * 1024) break;
-  }
-  if (A.rb < 1) return SIXDGS_E_UNSUPPORTED;
+  const size_t lds = P.lds_bytes;
   static size_t lds_set = 0;
   if (lds > lds_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_image_prep), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_image_prep), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ip::kLdsBudget);
     if (e != hipSuccess) return (int)e;
-    lds_set = 150 * 1024;
+    lds_set = ip::kLdsBudget;
   }
   hipLaunchKernelGGL(k_image_prep, dim3((unsigned)sdg_cdiv(out_size, A.rb), (unsigned)batch), dim3(256), lds, sdg_stream(stream), A);
   SDG_LAUNCH_OK();
