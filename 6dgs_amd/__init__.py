@@ -24,7 +24,7 @@ from .test import test_pose_estimation  # noqa: F401
 from .scene import CameraInfo  # noqa: F401
 from .distance_based_loss import DistanceBasedScoreLoss  # noqa: F401
 from .train import train_id_module  # noqa: F401
-from .render import render_views  # noqa: F401
+from .render import render_depth, render_views, surface_points  # noqa: F401
 from .autograd import photometric_loss, raster_views  # noqa: F401
 from .refine import refine_poses, refine_results  # noqa: F401
 from .evaluate import evaluate_views  # noqa: F401
@@ -34,4 +34,4 @@ from .contribution import prune_by_contribution, scene_contribution  # noqa: F40
 __all__ = ["GaussianModel", "GaussianScene", "CameraInfo", "generate_all_possible_rays", "IdentificationModule",
            "test_pose_estimation", "DistanceBasedScoreLoss", "train_id_module", "render_views", "raster_views", "photometric_loss",
            "refine_poses", "refine_results", "fit_scene", "evaluate_views", "scene_contribution",
-           "prune_by_contribution"]
+           "prune_by_contribution", "render_depth", "surface_points"]

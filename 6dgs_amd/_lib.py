@@ -64,6 +64,11 @@ SIGNATURES = {
     "sixdgs_scene_contrib_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
     "sixdgs_scene_contrib": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, i32, i32, C.c_float, i32, i64] + [vp] * 7
                              + [vp, vp, vp, sz, vp]),
+    "sixdgs_raster_depth_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
+    "sixdgs_raster_depth": (i32, [i64, i32, i32, i32, i64, vp, sz, vp] + [vp] * 5 + [i32, vp, sz, vp, C.POINTER(Profile)]),
+    "sixdgs_scene_depth_workspace_bytes": (sz, [i64, i32, i32, i32, i64]),
+    "sixdgs_scene_depth": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i64, vp, i32, i32, i32, C.c_float, vp, i32, i64] + [vp] * 5
+                           + [i32, vp, i32, vp, vp, vp, sz, vp]),
     "sixdgs_photometric_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "sixdgs_photometric_loss": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, vp, vp, sz, vp, C.POINTER(Profile)]),
     "sixdgs_pose_compose": (i32, [vp, vp, i32, vp, vp]),

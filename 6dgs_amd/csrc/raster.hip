@@ -12,7 +12,8 @@
 //
 // The backward (sixdgs_raster_views_backward: k_raster_blend_bwd, k_raster_project_bwd, k_raster_cams_bwd) is further down; it reads this
 // workspace and sorts nothing again.  So does the contribution pass behind it (sixdgs_raster_contrib: k_raster_contrib_walk,
-// k_raster_contrib_gather), which repeats the blend's walk and keeps alpha T per (view, Gaussian) instead of a colour.
+// k_raster_contrib_gather), which repeats the blend's walk and keeps alpha T per (view, Gaussian) instead of a colour, and the depth pass
+// behind that (sixdgs_raster_depth: k_raster_depth), which repeats it with the Gaussians' p.z as the colour and notes where T crosses 0.5.
 //
 // When the scene needs more than max_instances pairs, emit / ranges / blend read the total on the device and return; nothing is
 // written past a buffer, `instances` still receives the needed number.  No kernel here uses scratch or a global atomic, and every
@@ -1020,6 +1021,102 @@ __global__ __launch_bounds__(256) void k_raster_contrib_gather(ContribGatherArgs
 
 inline size_t contrib_bytes(int64_t max_instances) { return sdg_align((size_t)max_instances * sizeof(uint4)); }
 
+// ---- depth maps (include/sixdgs.h, sixdgs_raster_depth) ----------------------------------------------------------------------------
+//   walk    k_raster_depth    one workgroup per tile and view, one pixel per lane: the blend's walk, its arithmetic as k_raster_blend
+//           writes it, with one accumulator -- the depth channel D += (z alpha) T -- in the place of the three colours, and the first
+//           Gaussian behind which T is below 0.5.  Rounds of 256 staged in LDS: conic + opacity, centre, z and the Gaussian's index (8 KB);
+//           every lane reads the same entry (a broadcast).  Each pixel owns its elements of the outputs: no atomics, no scratch
+// Reads the forward's workspace, writes only the outputs.
+struct DepthArgs {
+  Records r;
+  const int64_t* total;
+  const int2* ranges;
+  const uint32_t *vals0, *vals1;
+  const uint32_t* which;
+  const float* cams;
+  float *expected, *median;
+  int32_t* median_index;
+  float *alpha, *points;
+  int64_t n, max_instances;
+  int width, height, gx, gy, points_kind;
+};
+
+__global__ __launch_bounds__(256) void k_raster_depth(DepthArgs B) {
+  __shared__ float4 s_co[256];
+  __shared__ float2 s_uv[256];
+  __shared__ float s_z[256];
+  __shared__ uint32_t s_id[256];
+  if (*B.total > B.max_instances) return;
+  const int tid = threadIdx.x, view = blockIdx.z;
+  const int2 rg = B.ranges[((int64_t)view * B.gy + blockIdx.y) * B.gx + blockIdx.x];
+  const uint32_t* __restrict__ vals = *B.which ? B.vals1 : B.vals0;
+  const int x = blockIdx.x * kTile + (tid & 15), y = blockIdx.y * kTile + (tid >> 4);
+  const bool inside = x < B.width && y < B.height;
+  const float xf = (float)x, yf = (float)y;
+  const int64_t rec0 = (int64_t)view * B.n;
+  bool done = !inside;
+  float T = 1.f, D = 0.f, med = 0.f;
+  int med_i = -1;
+  for (int base = rg.x; base < rg.y; base += 256) {
+    if (__syncthreads_and(done)) break;          // (also: everybody has left the previous round's LDS)
+    const int m = min(256, rg.y - base);
+    if (tid < m) {
+      const uint32_t i = vals[base + tid];
+      const int64_t rec = rec0 + i;
+      s_co[tid] = B.r.co[rec];
+      s_uv[tid] = B.r.uv[rec];
+      s_z[tid] = __uint_as_float(B.r.depth[rec]);
+      s_id[tid] = i;
+    }
+    __syncthreads();
+    for (int j = 0; !done && j < m; ++j) {
+      const float2 uv = s_uv[j];
+      const float4 co = s_co[j];
+      const float dx = (uv.x - xf) - 0.5f, dy = (uv.y - yf) - 0.5f;
+      const float power = -0.5f * ((co.x * dx) * dx + (co.z * dy) * dy) - (co.y * dx) * dy;
+      if (power > 0.f) continue;
+      const float alpha = fminf(0.99f, co.w * expf(power));
+      if (alpha < 1.f / 255.f) continue;
+      const float Tn = T * (1.f - alpha);
+      if (Tn < 1e-4f) {
+        done = true;
+        break;
+      }
+      D += (s_z[j] * alpha) * T;
+      if (med_i < 0 && Tn < 0.5f) {
+        med = s_z[j];
+        med_i = (int)s_id[j];
+      }
+      T = Tn;
+    }
+  }
+  if (!inside) return;
+  const float oa = 1.f - T;
+  const int64_t p = ((int64_t)view * B.height + y) * B.width + x;
+  if (B.expected) B.expected[p] = D;
+  if (B.median) B.median[p] = med;
+  if (B.median_index) B.median_index[p] = med_i;
+  if (B.alpha) B.alpha[p] = oa;
+  if (B.points) {
+    float X = 0.f, Y = 0.f, Z = 0.f;
+    if (B.points_kind == 0 ? med_i >= 0 : oa > 0.f) {
+      const float* __restrict__ cam = B.cams + 16 * (size_t)view;
+      const float d = B.points_kind == 0 ? med : D / oa;
+      // the point of the pixel's ray at camera depth d: q = d r - t, X = W^T q
+      const float qx = d * (((xf + 0.5f) - cam[14]) / cam[12]) - cam[3];
+      const float qy = d * (((yf + 0.5f) - cam[15]) / cam[13]) - cam[7];
+      const float qz = d - cam[11];
+      X = (cam[0] * qx + cam[4] * qy) + cam[8] * qz;
+      Y = (cam[1] * qx + cam[5] * qy) + cam[9] * qz;
+      Z = (cam[2] * qx + cam[6] * qy) + cam[10] * qz;
+    }
+    float* o = B.points + 3 * p;
+    o[0] = X; o[1] = Y; o[2] = Z;
+  }
+}
+
+constexpr size_t kDepthBytes = 256;          // the walk needs no workspace of its own: the siblings' smallest piece
+
 }  // namespace
 
 extern "C" {
@@ -1236,6 +1333,53 @@ int sixdgs_raster_contrib(int64_t n, int views, int width, int height, int64_t m
     SdgProfileScope t(prof, s, 0, 0);
     ContribGatherArgs A = {r.cnt, r.offs, slots, weight, peak, pixels, stops, seen, view_weight, view_pixels, n, max_instances, views};
     hipLaunchKernelGGL(k_raster_contrib_gather, dim3((unsigned)sdg_cdiv(n, 256)), dim3(256), 0, s, A);
+    SDG_LAUNCH_OK();
+  }
+  return 0;
+}
+
+size_t sixdgs_raster_depth_workspace_bytes(int64_t n, int views, int width, int height, int64_t max_instances) {
+  if (!sizes_ok(n, views, width, height, max_instances)) return 0;
+  return kDepthBytes;
+}
+
+int sixdgs_raster_depth(int64_t n, int views, int width, int height, int64_t max_instances, const void* fwd_ws, size_t fwd_ws_bytes,
+                        const float* cams, float* expected, float* median, int32_t* median_index, float* alpha, float* points,
+                        int points_kind, void* ws, size_t ws_bytes, sixdgs_stream_t stream, sixdgs_profile* prof) {
+  SDG_CHECK_ARG(sizes_ok(n, views, width, height, max_instances));
+  SDG_CHECK_ARG(points_kind == 0 || points_kind == 1);
+  if (views == 0) return 0;
+  SDG_CHECK_ARG(fwd_ws && (cams || !points));
+  SDG_CHECK_ARG(rp::aligned4(cams) && rp::aligned4(expected) && rp::aligned4(median) && rp::aligned4(median_index) && rp::aligned4(alpha) &&
+                rp::aligned4(points));
+  const Layout F = layout(n, views, width, height, max_instances);
+  if (fwd_ws_bytes < F.total || ws_bytes < kDepthBytes) return SIXDGS_E_WORKSPACE;
+  SDG_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0 && ((uintptr_t)fwd_ws & 255) == 0);
+  if (!(expected || median || median_index || alpha || points)) return 0;
+  hipStream_t s = sdg_stream(stream);
+  const size_t px = (size_t)views * (size_t)height * (size_t)width;
+  if (n == 0) {           // no Gaussian, no list: every pixel keeps the values it starts the walk with
+    float* const zeroed[] = {expected, median, alpha};
+    for (float* o : zeroed)
+      if (o) {
+        const hipError_t e = hipMemsetAsync(o, 0, px * sizeof(float), s);
+        if (e != hipSuccess) return (int)e;
+      }
+    hipError_t e = median_index ? hipMemsetAsync(median_index, 0xFF, px * sizeof(int32_t), s) : hipSuccess;
+    if (e == hipSuccess && points) e = hipMemsetAsync(points, 0, px * 3 * sizeof(float), s);
+    return (int)e;
+  }
+  const char* f = (const char*)fwd_ws;
+  const int gx = (int)sdg_cdiv(width, kTile), gy = (int)sdg_cdiv(height, kTile);
+  const int64_t vn = (int64_t)views * n;
+  Records r = {(float4*)(f + F.co), (float2*)(f + F.uv), (float*)(f + F.rgb), (uint32_t*)(f + F.depth), (ushort4*)(f + F.rect),
+               (int64_t*)(f + F.cnt), (int64_t*)(f + F.offs)};
+  {
+    SdgProfileScope t(prof, s, 0, 0);
+    DepthArgs B = {r, r.offs + vn, (const int2*)(f + F.ranges), (const uint32_t*)(f + F.vals0), (const uint32_t*)(f + F.vals1),
+                   (const uint32_t*)(f + F.scan_tmp), cams, expected, median, median_index, alpha, points, n, max_instances, width, height,
+                   gx, gy, points_kind};
+    hipLaunchKernelGGL(k_raster_depth, dim3((unsigned)gx, (unsigned)gy, (unsigned)views), dim3(256), 0, s, B);
     SDG_LAUNCH_OK();
   }
   return 0;

@@ -635,6 +635,132 @@ def scene_contrib_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, ca
     return out
 
 
+# the maps of sixdgs_raster_depth, in the order its entry points take them (points, [V,H,W,3], comes behind them)
+DEPTH_MAPS = (("expected", torch.float32), ("median", torch.float32), ("median_index", torch.int32), ("alpha", torch.float32))
+DEPTH_POINTS = {"median": 0, "expected": 1}
+DEPTH_STATUS_CAPACITY = 2
+
+
+def _depth_want(want, points):
+    want = tuple(want)
+    if any(w not in dict(DEPTH_MAPS) for w in want):
+        raise ValueError(f"want must name some of {tuple(k for k, _ in DEPTH_MAPS)} (got {want})")
+    if points is not None and points not in DEPTH_POINTS:
+        raise ValueError(f"points must be None, 'median' or 'expected' (got {points!r})")
+    if not want and points is None:
+        raise ValueError("nothing asked for: want is empty and points is None")
+    return want
+
+
+def raster_depth_workspace_bytes(n: int, views: int, width: int, height: int, max_instances: int) -> int:
+    return int(_lib.load().sixdgs_raster_depth_workspace_bytes(int(n), int(views), int(width), int(height), int(max_instances)))
+
+
+@_on_device
+def raster_depth(state, n: int, views: int, width: int, height: int, *, cams: Optional[torch.Tensor] = None,
+                 want=("expected", "median", "median_index", "alpha"), points: Optional[str] = None,
+                 workspace: Optional[torch.Tensor] = None, profile: Optional[Profile] = None) -> dict:
+    """The depth maps of the views of one forward (sixdgs_raster_depth in include/sixdgs.h defines them): state = the (workspace,
+    capacity) pair of raster_views(..., want_state=True) on n Gaussians and `views` rows at width x height, not written since.  Returns
+    a dict with the maps named in `want`, [V,height,width] each -- expected (the blend's depth channel, un-normalised), median, alpha
+    float32, median_index int32 (-1: T stayed at or above 0.5) -- and with points="median" | "expected" the world points
+    [V,height,width,3] at that depth (zeros where the pixel has none); these need cams [V,16], the forward's rows."""
+    if (not isinstance(state, (tuple, list)) or len(state) != 2 or not torch.is_tensor(state[0])
+            or not 1 <= int(state[1]) <= RASTER_MAX_INSTANCES):
+        raise ValueError("state must be the (workspace, capacity) pair of raster_views(..., want_state=True)")
+    fwd_ws, capacity = state[0], int(state[1])
+    n, views, width, height = int(n), int(views), int(width), int(height)
+    if n < 0 or views < 0 or width < 1 or height < 1:
+        raise ValueError(f"n and views must not be negative, width and height positive (got {n}, {views}, {width} x {height})")
+    want = _depth_want(want, points)
+    if points is not None:
+        if not torch.is_tensor(cams) or tuple(cams.shape) != (views, 16):
+            raise ValueError(f"points need cams, the forward's [{views},16] rows (got {tuple(cams.shape) if torch.is_tensor(cams) else type(cams).__name__})")
+        cams = _f32(cams)
+    else:
+        cams = None
+    dev = fwd_ws.device
+    _need_gpu(fwd_ws, cams, workspace)
+    lib = _lib.load()
+    need = lib.sixdgs_raster_depth_workspace_bytes(n, views, width, height, capacity)
+    if need == 0:
+        raise ValueError(f"sizes outside the rasteriser's limits (n {n}, views {views}, {width} x {height}, instances {capacity})")
+    ws, ws_bytes = _workspace(workspace, need, dev)
+    res = {k: torch.empty(views, height, width, dtype=dt, device=dev) for k, dt in DEPTH_MAPS if k in want}
+    if points is not None:
+        res["points"] = torch.empty(views, height, width, 3, dtype=torch.float32, device=dev)
+    check(lib.sixdgs_raster_depth(n, views, width, height, capacity, _p(fwd_ws), fwd_ws.numel() * fwd_ws.element_size(), _p(cams),
+                                  *[_p(res.get(k)) for k, _ in DEPTH_MAPS], _p(res.get("points")), DEPTH_POINTS.get(points, 0), _p(ws), ws_bytes,
+                                  _stream(), profile),
+          "raster_depth")
+    return res
+
+
+def scene_depth_workspace_bytes(n: int, chunk: int, width: int, height: int, max_instances: int) -> int:
+    return int(_lib.load().sixdgs_scene_depth_workspace_bytes(int(n), int(chunk), int(width), int(height), int(max_instances)))
+
+
+@_on_device
+def scene_depth_raw(xyz, scale, rot, opacity, f_dc, f_rest, sh_degree: int, cams: torch.Tensor, width: int, height: int, *,
+                    want=("expected", "median", "median_index", "alpha"), points: Optional[str] = None, want_image: bool = False,
+                    channels: int = 3, chunk: int = 8, scale_modifier: float = 1.0, background=(1.0, 1.0, 1.0), scale_is_log: bool = True,
+                    opacity_is_logit: bool = True, max_instances: Optional[int] = None, retry: bool = True,
+                    workspace: Optional[torch.Tensor] = None) -> dict:
+    """The depth maps of the views cams [V,16] as ONE library call (sixdgs_scene_depth in include/sixdgs.h): chunks of `chunk` views,
+    each rasterised and walked on the device, nothing read back in between.  max_instances is the capacity of one chunk.  Returns a
+    dict: the maps named in `want` and `points` as raster_depth returns them, image (uint8 [V,height,width,channels], the rasteriser's
+    own image of the same pass, with want_image), status (int32 [1]; bit 1: a chunk did not fit the capacity and its rows are as they
+    were allocated: zeros, median_index -1), instances_needed and max_instances (ints).  The call reads status and instances_needed
+    once at the end and -- with retry -- on bit 1 runs once more with the needed capacity."""
+    if isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError(f"chunk must be a positive integer (got {chunk!r})")
+    if channels not in (3, 4):
+        raise ValueError(f"channels must be 3 or 4 (got {channels})")
+    want = _depth_want(want, points)
+    cams, width, height = _view_args(cams, width, height, background, scale_modifier)
+    scene, n, n_coef = _scene(xyz, scale, rot, opacity, f_dc, f_rest)
+    views = cams.shape[0]
+    chunk = max(min(int(chunk), views), 1)
+    capacity = _capacity(max_instances, n, chunk)
+    _need_gpu(*scene, cams, workspace)
+    lib = _lib.load()
+    dev = scene[0].device
+    bg = _background(background, dev)
+    out = {k: torch.zeros(views, height, width, dtype=dt, device=dev) for k, dt in DEPTH_MAPS if k in want}
+    if "median_index" in out:
+        out["median_index"].fill_(-1)
+    if points is not None:
+        out["points"] = torch.zeros(views, height, width, 3, dtype=torch.float32, device=dev)
+    if want_image:
+        out["image"] = torch.zeros(views, height, width, int(channels), dtype=torch.uint8, device=dev)
+    out["status"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    needed_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    needed = 0
+    for attempt in range(2):
+        need = lib.sixdgs_scene_depth_workspace_bytes(n, chunk, width, height, capacity)
+        if need == 0:
+            raise ValueError(f"sizes outside the rasteriser's limits (n {n}, chunk {chunk}, {width} x {height}, instances {capacity})")
+        ws, ws_bytes = _workspace(workspace, need, dev)
+        check(lib.sixdgs_scene_depth(*_scene_args(scene, n_coef, scale_is_log, opacity_is_logit), int(sh_degree), int(n_coef), n, _p(cams),
+                                     views, width, height, float(scale_modifier), _p(bg), chunk, capacity,
+                                     *[_p(out.get(k)) for k, _ in DEPTH_MAPS], _p(out.get("points")), DEPTH_POINTS.get(points, 0),
+                                     _p(out.get("image")), int(channels), _p(out["status"]), _p(needed_t), _p(ws), ws_bytes, _stream()),
+              "scene_depth")
+        if views == 0:
+            break
+        # the one host read of the call: the status word and the largest instance count seen
+        flags = torch.cat([out["status"].to(torch.int64), needed_t]).cpu()
+        needed = int(flags[1])
+        if not retry or not int(flags[0]) & DEPTH_STATUS_CAPACITY:
+            break
+        if attempt == 1 or needed > RASTER_MAX_INSTANCES:
+            raise RuntimeError(f"6dgs_amd: scene_depth needs {needed} tile instances per chunk (limit 2^31 - 1): use a smaller chunk")
+        capacity = needed
+    out["instances_needed"] = needed
+    out["max_instances"] = capacity
+    return out
+
+
 def photometric_loss_workspace_bytes(views: int, width: int, height: int, want_grad: bool = False) -> int:
     return int(_lib.load().sixdgs_photometric_loss_workspace_bytes(int(views), int(width), int(height), int(bool(want_grad))))
 

@@ -109,3 +109,97 @@ def render_views(scene: GaussianScene, cameras: Sequence, *, rgba: bool = False,
     host = [im.cpu().numpy() for im in images]
     out = [_as_camera_info(c, h) for c, h in zip(cameras, host)]
     return (out, images) if return_device else out
+
+
+DEPTH_KINDS = ("median", "expected")
+
+
+def _depth_groups(scene, cameras, kind, points, want_image, chunk, scale_modifier, background=(1.0, 1.0, 1.0)):
+    """The raw depth call per group of cameras of one size -> [(indices of the group's cameras, ops.scene_depth_raw's dict)]."""
+    if kind not in DEPTH_KINDS:
+        raise ValueError(f"kind must be 'median' or 'expected' (got {kind!r})")
+    if isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError(f"chunk must be a positive integer (got {chunk!r})")
+    if not (float(scale_modifier) > 0.0 and float(scale_modifier) < float("inf")):
+        raise ValueError(f"scale_modifier must be positive and finite (got {scale_modifier})")
+    cameras = list(cameras)
+    rows = camera_rows(cameras)
+    if not scene.get_xyz.is_cuda:
+        raise RuntimeError("6dgs_amd: depth maps need the scene on the GPU (no CPU fallback on the product path)")
+    sizes = [(int(_field(c, "width")), int(_field(c, "height"))) for c in cameras]
+    dev = scene.get_xyz.device
+    want = ("median", "median_index", "alpha") if kind == "median" else ("expected", "alpha")
+    groups = []
+    for size in sorted(set(sizes)):
+        which = [i for i, s in enumerate(sizes) if s == size]
+        raw = ops.scene_depth_raw(scene._xyz, scene._scaling, scene._rotation, scene._opacity, scene._features_dc, scene._features_rest,
+                                  scene.active_sh_degree, torch.from_numpy(rows[which]).to(dev), size[0], size[1], want=want,
+                                  points=kind if points else None, want_image=want_image, chunk=int(chunk), scale_modifier=scale_modifier,
+                                  background=background)
+        groups.append((which, raw))
+    return cameras, groups
+
+
+def _depth_of(raw, kind):
+    """(depth, valid) [V,H,W] of one raw call: the median, or expected / alpha where alpha > 0 and 0 elsewhere."""
+    if kind == "median":
+        return raw["median"], raw["median_index"] >= 0
+    valid = raw["alpha"] > 0
+    return torch.where(valid, raw["expected"] / raw["alpha"], torch.zeros_like(raw["expected"])), valid
+
+
+@torch.no_grad()
+def render_depth(scene: GaussianScene, cameras: Sequence, *, kind: str = "median", points: bool = False, chunk: int = 8,
+                 scale_modifier: float = 1.0, return_device: bool = False) -> dict:
+    """Depth maps of the views the 3DGS rasteriser renders (ops.scene_depth_raw; sixdgs_raster_depth in include/sixdgs.h defines
+    them).  kind="median": the camera depth of the Gaussian that takes the pixel's transmittance below one half; "expected": the
+    alpha-weighted mean depth of what the pixel saw, expected / alpha.  Returns a dict of lists, one entry per camera in the order
+    given: depth float32 [H,W] (0 where there is none), alpha float32 [H,W], valid bool [H,W]; with kind="median" index int32 [H,W]
+    (that Gaussian, -1 where there is none); with points=True points float32 [H,W,3], the world point of the pixel's ray at `depth`
+    (zeros where not valid).  When every camera has the same size the entries are stacked to [V,H,W(,3)] arrays instead.  Cameras of
+    one size are rendered together, `chunk` views per launch; the maps do not depend on it.  numpy arrays, or with return_device
+    GPU tensors."""
+    cameras, groups = _depth_groups(scene, cameras, kind, bool(points), False, chunk, scale_modifier)
+    keys = ("depth", "alpha", "valid") + (("index",) if kind == "median" else ()) + (("points",) if points else ())
+    out = {k: [None] * len(cameras) for k in keys}
+    for which, raw in groups:
+        depth, valid = _depth_of(raw, kind)
+        maps = {"depth": depth, "alpha": raw["alpha"], "valid": valid, "index": raw.get("median_index"), "points": raw.get("points")}
+        for j, i in enumerate(which):
+            for k in keys:
+                out[k][i] = maps[k][j]
+    if len(groups) <= 1:
+        out = {k: (torch.stack(v) if v else torch.empty(0)) for k, v in out.items()}
+        return out if return_device else {k: v.cpu().numpy() for k, v in out.items()}
+    return out if return_device else {k: [t.cpu().numpy() for t in v] for k, v in out.items()}
+
+
+@torch.no_grad()
+def surface_points(scene: GaussianScene, cameras: Sequence, *, min_alpha: float = 0.5, stride: int = 1, kind: str = "median",
+                   chunk: int = 8, scale_modifier: float = 1.0, background=(1.0, 1.0, 1.0)):
+    """A surface point cloud from views: the world points (render_depth's `points`) of every `stride`-th pixel, in x and in y, that is
+    valid and has alpha >= min_alpha, coloured from the rasteriser's uint8 image of the same pass.  Returns GPU tensors (xyz float32
+    [M,3], rgb uint8 [M,3], view int32 [M] -- the camera's position in `cameras` --, pixel int32 [M,2] = (x, y)), ordered by size
+    group, then view, then row-major pixel; GaussianScene.from_points(xyz, rgb / 255) re-seeds a scene from them."""
+    if not 0.0 <= float(min_alpha) <= 1.0:
+        raise ValueError(f"min_alpha must be in [0, 1] (got {min_alpha})")
+    if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
+        raise ValueError(f"stride must be a positive integer (got {stride!r})")
+    if len(background) != 3:
+        raise ValueError("background must have 3 entries")
+    cameras, groups = _depth_groups(scene, cameras, kind, True, True, chunk, scale_modifier, background)
+    dev = scene.get_xyz.device
+    parts = []
+    for which, raw in groups:
+        _, valid = _depth_of(raw, kind)
+        keep = valid & (raw["alpha"] >= float(min_alpha))
+        grid = torch.zeros_like(keep)
+        grid[:, ::int(stride), ::int(stride)] = True
+        keep &= grid
+        v, y, x = torch.nonzero(keep, as_tuple=True)
+        parts.append((raw["points"][keep], raw["image"][keep][:, :3], torch.tensor(which, dtype=torch.int32, device=dev)[v],
+                      torch.stack([x, y], dim=1).to(torch.int32)))
+    if not parts:
+        return (torch.empty(0, 3, device=dev), torch.empty(0, 3, dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty(0, 2, dtype=torch.int32, device=dev))
+    return tuple(torch.cat([p[k] for p in parts]) for k in range(4))

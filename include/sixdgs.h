@@ -342,6 +342,71 @@ int sixdgs_scene_contrib(const float* xyz, const float* scale, int scale_is_log,
                          int32_t* status /*[1]*/, int64_t* instances_needed /*[1]*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Depth maps of views (additive in ABI 10): how far away what a pixel of sixdgs_raster_views shows is -- the blend of step 11 with the
+ * Gaussians' camera depth p.z in the place of a colour (`expected`), the depth at which the pixel's transmittance falls below one half
+ * (`median`, with the Gaussian that takes it there), 1 - T, and the world point of the pixel's ray at either depth.  All arithmetic in
+ * fp32, no contraction into fused multiply-adds.
+ *
+ * fwd_ws is the workspace of a COMPLETED sixdgs_raster_views call with the same n, views, width, height and max_instances, whose
+ * instance count fitted, not written since (whether that call produced an image does not matter; the scene is in fwd_ws already and is
+ * not passed again); it is not written here.  For view v and pixel (x, y) inside the image the walk of step 11 is repeated operation by
+ * operation over the same ordered list -- d, power, the skip when power > 0, alpha_j = min(0.99, o exp(power)), the skip when
+ * alpha_j < 1/255, T' = T (1 - alpha_j), the stop when T' < 1e-4 -- so that every skip and the stop fall exactly where the forward's
+ * did.  z_j is the float whose bits the forward stored for the Gaussian (step 1's p.z, the sort key of step 10).  With T = 1, D = 0 and
+ * no median to begin with, for each Gaussian j the pixel ADDS (neither skipped nor the stopper), in order:
+ *   1. D += (z_j alpha_j) T, T the value before j: the colour channels' form with c = z_j;
+ *   2. if no median has been taken yet and T' < 0.5: median = z_j, median_index = i_j, the Gaussian's index in the scene;
+ *   3. T = T'.
+ * The stop cannot swallow a median: the Gaussian that takes T from >= 0.5 to below it has T' >= 0.5 (1 - 0.99) = 0.005 > 1e-4, so it
+ * is always added.  As the backward takes 1 - T for a fourth colour channel of colour 1, D is a fifth of colour z_j and background 0.
+ * Outputs, each may be NULL, [views][height][width], WRITTEN, NOT ACCUMULATED, one owner per element:
+ *   expected      fp32  D, UN-NORMALISED: the depth channel of the blend; expected / alpha is the mean depth of what the pixel saw;
+ *   median        fp32  and median_index int32: 0.f and -1 where T never fell below 0.5;
+ *   alpha         fp32  1 - T of the end of the walk: THE SAME BITS as channel 3 of the forward's image_f32;
+ *   points        fp32  [views][height][width][3]: the world point on the pixel's ray at camera depth d, d = median (points_kind 0) or
+ *                 expected / alpha (points_kind 1).  With the view's row of cams = [W | t], fx, fy, cx, cy (the forward's row; cams is
+ *                 needed only for points and may be NULL otherwise): r = ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1), q = d r - t,
+ *                 X = W^T q, each of the three dot products as (a + b) + c in index order.  Exact (0, 0, 0) where the pixel has no depth of
+ *                 that kind: median_index < 0, respectively alpha == 0.  Validity is those two and is not encoded in the point.
+ * SAME INPUT, SAME BYTES on every call: no atomics at all.  VIEWS DO NOT MIX: a view's maps are the same bits whether it is walked alone
+ * or in a batch.  Pixels of a ragged last tile that lie outside the image are never written.  If the recorded instance total exceeds
+ * max_instances the kernel reads that on the device and returns with EVERY OUTPUT UNTOUCHED.  views == 0 returns 0; n == 0 writes the
+ * values of a pixel with an empty list: 0, 0, -1, 0 and zero points; a call with every output NULL returns 0 without a launch.
+ * Limits and argument errors are the forward's, plus points_kind outside {0, 1}, a NULL fwd_ws, points without cams and misaligned
+ * outputs or cams (4 bytes): SIXDGS_E_BADARG; a fwd_ws_bytes below sixdgs_raster_views_workspace_bytes or a ws_bytes below
+ * sixdgs_raster_depth_workspace_bytes: SIXDGS_E_WORKSPACE; all answered without touching a GPU.  The walk needs no workspace of its own:
+ * sixdgs_raster_depth_workspace_bytes, answered without a GPU, is 256 inside the limits and 0 outside them, and ws (256-byte aligned) is
+ * not written.  One 256-thread workgroup per tile and view, one pixel per lane, the list staged through LDS in rounds of 256 (conic and
+ * opacity, centre, z, index: 8 KB).  prof (may be NULL) receives one slot: walk.
+ *
+ * sixdgs_scene_depth renders the maps of many views as one call.  Scene arrays, flags, sh_degree and scale_modifier as
+ * sixdgs_raster_views takes them; cams [views][16]; the five outputs over all views, and optionally image_u8
+ * [views][height][width][channels] (channels 3 or 4) -- the forward's own uint8 image over `background` ([3] device, needed only with
+ * image_u8), so that the colours of a point cloud come from the same pass.  It zeroes status[0] and instances_needed[0], then for each
+ * chunk of up to `chunk` (>= 1) consecutive rows of cams enqueues on `stream`, through the entry points as they are:
+ * sixdgs_raster_views of the chunk's rows into the chunk's rows of image_u8 (without image_u8: no image, its blend does not run; the
+ * count stays on the device), sixdgs_raster_depth into the chunk's rows of the outputs, and a record: instances_needed[0] =
+ * max(instances_needed[0], count); if count > max_instances, bit 1 of status[0] is set and that chunk's rows of every output, image_u8
+ * included, are left as they were; other chunks are unaffected.  No host synchronisation, no device-to-host copy, no allocation; when
+ * it returns, the work is enqueued.  Given a capacity that fits, every output is the same bytes for every chunk.  Limits and errors are
+ * the parts'; views == 0 returns 0.  sixdgs_scene_depth_workspace_bytes is answered without a GPU and is 0 outside the limits: the two
+ * parts' workspaces at `chunk` views and the count, each piece rounded up to 256 B. */
+size_t sixdgs_raster_depth_workspace_bytes(int64_t n, int views, int width, int height, int64_t max_instances);
+int sixdgs_raster_depth(int64_t n, int views, int width, int height, int64_t max_instances, const void* fwd_ws, size_t fwd_ws_bytes,
+                        const float* cams /*[views][16] or NULL*/, float* expected /*[views][height][width]*/,
+                        float* median /*[views][height][width]*/, int32_t* median_index /*[views][height][width]*/,
+                        float* alpha /*[views][height][width]*/, float* points /*[views][height][width][3]*/,
+                        int points_kind /*0 median, 1 expected / alpha*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream,
+                        sixdgs_profile* prof);
+size_t sixdgs_scene_depth_workspace_bytes(int64_t n, int chunk, int width, int height, int64_t max_instances);
+int sixdgs_scene_depth(const float* xyz, const float* scale, int scale_is_log, const float* rot, const float* opacity, int opacity_is_logit,
+                       const float* f_dc, const float* f_rest, int sh_degree, int n_coef, int64_t n, const float* cams /*[views][16]*/,
+                       int views, int width, int height, float scale_modifier, const float* background /*[3] device or NULL*/, int chunk,
+                       int64_t max_instances, float* expected, float* median, int32_t* median_index, float* alpha, float* points,
+                       int points_kind, uint8_t* image_u8 /*or NULL*/, int channels /*3 or 4*/, int32_t* status /*[1]*/,
+                       int64_t* instances_needed /*[1]*/, void* ws, size_t ws_bytes, sixdgs_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The photometric loss of render-and-compare (additive in ABI 10): per view loss_v = (1 - lambda) L1 + lambda (1 - SSIM) between an
  * image a and a target b, and grad_image = grad_loss[v] d loss_v / d a.  It is the reference's training objective (train.py:119 with
  * lambda_dssim = 0.2; utils/loss_utils.py: 11 x 11 Gaussian window, sigma 1.5, padding 5, one group per channel).  All arithmetic in
